@@ -16,7 +16,15 @@ timed on this host over config 0's sample (rank 0, N=1 only).  `pinned_h2d` = th
 (64 MiB chunks streamed from pinned host memory; `zero_copy_gbs` the same bytes read in place from
 registered pageable memory), aggregated over all ranks.
 
+A plain run sets up, warms up, times the K steps and prints the line; `bit_exact`,
+`pinned_h2d` and `cpu_baseline` are null in it.  `--full` adds those legs after the timed
+steps: the golden-table comparison, the pinned-host H2D leg and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (the digest table; with
+N > 1 also the all-gathered node table) as DIR/<name>.npy, float64; the synthetic input is
+seeded, so two builds run with the same arguments can be compared digest for digest.
+
   python bench.py [--gpus N] [--steps K] [--warmup W] [--chunks C] [--chunk-mib M]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline] [--h2d-chunks H]]
   torchrun --nproc-per-node N bench.py --gpus N ...
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE) starts the N ranks itself as a child
 torch.distributed.run; a --gpus that disagrees with WORLD_SIZE exits non-zero.
@@ -46,12 +54,33 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--chunks", type=int, default=4096)
     ap.add_argument("--chunk-mib", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the golden-table comparison (bit_exact), "
+                         "the pinned-host H2D leg and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0 = every core this job may use: affinity and cgroup quota)")
     ap.add_argument("--h2d-chunks", type=int, default=16,
-                    help="64 MiB chunks per GPU in the pinned-host H2D leg (0 = skip)")
-    return ap.parse_args()
+                    help="with --full: 64 MiB chunks per GPU in the pinned-host H2D leg (0 = skip)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(path, arrays, budget_bytes=64 << 20):
+    """--dump-outputs: each array as path/<name>.npy in float64 (a uint32 digest or a chunk id is
+    exact there), budget_bytes (64 MB) in all at the most: a larger array is cut to a fixed, seeded sample of
+    its elements, the same from run to run."""
+    os.makedirs(path, exist_ok=True)
+    budget = budget_bytes // len(arrays) // 8  # elements per array
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if a.size > budget:
+            a = a[np.sort(np.random.default_rng(SEED).choice(a.size, budget, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def host_cpus():
@@ -394,14 +423,23 @@ def main():
     allreduce(t, dist.ReduceOp.MAX)
     elapsed, launch_ms_max, coll_ms_max = float(t[0]), float(t[1]), float(t[2])
 
-    # bit-exactness: the whole digest table (every rank's, and the all-gathered
+    # what the last timed step handed its caller: this rank's digests (rank 0's are written)
+    # and, in the distributed branch, the all-gathered node table
+    if args.dump_outputs and rank == 0:
+        arrays = {"digests": out.cpu().numpy().view(np.uint32)}
+        if use_dist:
+            arrays["node_ids"] = gathered[0][0].cpu().numpy()
+            arrays["node_crcs"] = gathered[0][1].cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
+
+    # bit-exactness (--full): the whole digest table (every rank's, and the all-gathered
     # node table, compared where it was gathered) against the oracle's
     # full-size golden table, committed data (tests/golden/make_bulk_golden.py);
     # no oracle code runs on this leg.
     gdir = os.path.join(REPO, "tests", "golden")
     golden = None
     gname = f"bulk_{args.chunk_mib}MiB_digests"
-    if os.path.exists(os.path.join(gdir, gname + ".json")):
+    if args.full and os.path.exists(os.path.join(gdir, gname + ".json")):
         with open(os.path.join(gdir, gname + ".json")) as f:
             gmeta = json.load(f)
         if length == gmeta["chunk_bytes"] and world * n <= gmeta["chunks"]:
@@ -414,7 +452,7 @@ def main():
             g_ids, g_crcs = gathered[0]
             bit_exact = (bit_exact and bool(torch.equal(g_ids, torch.arange(world * n, device=dev)))
                          and bool(torch.equal(g_crcs, golden.to(torch.int64) & 0xFFFFFFFF)))
-    if use_dist:  # codes ordered so that MAX keeps a failure: 0 unchecked, 1 ok, 2 mismatch
+    if use_dist and args.full:  # codes ordered so that MAX keeps a failure: 0 unchecked, 1 ok, 2 mismatch
         flag = torch.tensor([0 if bit_exact is None else (1 if bit_exact else 2)], device=dev)
         allreduce(flag, dist.ReduceOp.MAX)
         bit_exact = None if int(flag.item()) == 0 else int(flag.item()) == 1
@@ -432,7 +470,7 @@ def main():
                        f"separate rocprofv3 --pmc passes of this command, NOT counted in this run")
 
     h2d = None
-    if args.h2d_chunks > 0:
+    if args.full and args.h2d_chunks > 0:
         if use_dist:
             dist.barrier()
         sec, zsec, nbytes, ok = h2d_leg(L, hf, dev, rank, args.h2d_chunks)
@@ -457,6 +495,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -486,7 +525,7 @@ def main():
                                      "argsort (rank 0's mean; max over ranks beside it)"}
                            if use_dist else None),
         }
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N=1 only
             del buf
             torch.cuda.empty_cache()
             line["cpu_baseline"] = cpu_baseline(args.cpu_threads, L, hf, dev)

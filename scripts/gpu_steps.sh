@@ -20,7 +20,7 @@ for step in "$@"; do
     libtests) HF3FS_CRC_LIB=$PWD/3fs_amd/lib/ab/$LIBTEST.so run libtests_$LIBTEST 600 \
                 python -u -m pytest tests -m gpu -v --timeout 180 --timeout-method thread -k "not cpp and not bench_" ;;
     smoke) run smoke 120 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python -u bench.py ;;
+    bench) run bench 300 python -u bench.py --full ;;
     profile) echo "== profile ($(date +%T))"; bash scripts/gpu_profile.sh; rc=$?; echo "profile rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     suite) run suite 900 python -u tests/bench_suite.py ${SUITE_CASES:-} ;;
     soak) run soak $(( ${SOAK_SECONDS:-240} + 120 )) python -u tests/soak.py ${SOAK_SECONDS:-240} ;;

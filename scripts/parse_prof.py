@@ -43,7 +43,7 @@ def main():
     out = {
         "round": rnd,
         "kernel": rows[0]["Kernel_Name"] if rows else kernel,
-        "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py (defaults: --steps 20 --warmup 3); "
+        "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full (defaults: --steps 20 --warmup 3); "
                    "PMC: separate --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py --steps 3 --warmup 1",
         "launches": len(durs),
         "kernel_ms_mean": round(statistics.mean(durs), 4),

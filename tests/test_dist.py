@@ -100,6 +100,27 @@ def test_bench_gpus_launch_decision():
     assert cmd[-4:] == ["--gpus", "4", "--steps", "5"] and cmd[-5].endswith("bench.py")
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.dump_outputs: float64 files that hold uint32 digests exactly; an array over its
+    share of the size budget is cut to the same seeded sample in every run."""
+    import importlib
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, repo)
+    bench = importlib.import_module("bench")
+    crcs = np.array([0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF], dtype=np.uint32)
+    big = np.arange(1000, dtype=np.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"digests": crcs, "node_ids": big}, budget_bytes=2 * 8 * 100)
+    got = np.load(tmp_path / "a" / "digests.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), crcs)
+    ids = np.load(tmp_path / "a" / "node_ids.npy")
+    assert ids.dtype == np.float64 and ids.size == 100 and np.all(np.diff(ids) > 0) and ids.max() < 1000
+    assert np.array_equal(ids, np.load(tmp_path / "b" / "node_ids.npy"))
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "a").iterdir()) <= 2 * 8 * 100
+
+
 def test_bench_gpus_mismatch_exits_nonzero():
     """The mismatch check runs before anything touches a GPU, so it is exercised on the CPU."""
     import subprocess
