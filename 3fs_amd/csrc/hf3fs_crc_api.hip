@@ -125,6 +125,21 @@ hipError_t owned_malloc(void** p, size_t bytes, bool capturing) {
   return e;
 }
 
+// The calling thread in relaxed capture mode for a scope (back to the caller's mode at its
+// end): what the library allocates or creates for itself inside -- never a graph node -- is
+// neither rejected as capture-unsupported nor invalidates a capture when the call sits inside
+// one (torch.cuda.graph's default mode is global).
+struct RelaxedCapture {
+  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+  hipError_t err;
+  RelaxedCapture() : err(hipThreadExchangeStreamCaptureMode(&mode)) {}
+  ~RelaxedCapture() {
+    if (err == hipSuccess) (void)hipThreadExchangeStreamCaptureMode(&mode);
+  }
+  RelaxedCapture(const RelaxedCapture&) = delete;
+  RelaxedCapture& operator=(const RelaxedCapture&) = delete;
+};
+
 // ---- Scratch of calls captured into graphs ------------------------------------------
 // Every captured call gets device memory of its own (ticket counter, balance region,
 // verify values, batch scratch), owned by the graph it was captured into.  One owner
@@ -361,7 +376,9 @@ struct Context {
   uint32_t hint_next = 0;
   int hint_word(hipStream_t s, uint64_t** host, uint64_t** dev) {
     std::lock_guard<std::mutex> lk(mu);
-    if (!hint_host) {
+    if (!hint_host) {  // (the pair's first update call may be a captured one)
+      RelaxedCapture relaxed;
+      HIP_OR_FAIL(relaxed.err);
       HIP_OR_FAIL(hipHostMalloc((void**)&hint_host, kHintSlots * 8, hipHostMallocMapped | hipHostMallocCoherent));
       memset(hint_host, 0, kHintSlots * 8);
       HIP_OR_FAIL(hipHostGetDevicePointer((void**)&hint_dev, hint_host, 0));
@@ -452,11 +469,26 @@ int get_context(Context** out) {
     build_short_tables(host->sh[1], kPolyCrc32);
     build_fold_tables(host->fold[0], kPolyCrc32c);
     build_fold_tables(host->fold[1], kPolyCrc32);
-    HIP_OR_FAIL(hipMalloc(&c->tables, sizeof(DeviceTables)));
-    HIP_OR_FAIL(hipMemcpy(c->tables, host.get(), sizeof(DeviceTables), hipMemcpyHostToDevice));
-    HIP_OR_FAIL(hipMalloc(&c->diag, sizeof(hf3fs_crc_anomaly)));
+    // The process's first library call may sit inside a stream capture: the allocations in
+    // relaxed capture mode, the uploads on a stream of their own and waited for there (nothing
+    // touches the null stream or the capturing one).
+    RelaxedCapture relaxed;
+    HIP_OR_FAIL(relaxed.err);
     const hf3fs_crc_anomaly none{};
-    HIP_OR_FAIL(hipMemcpy(c->diag, &none, sizeof(none), hipMemcpyHostToDevice));
+    hipStream_t up = nullptr;
+    HIP_OR_FAIL(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+    hipError_t e = hipMalloc(&c->tables, sizeof(DeviceTables));
+    if (e == hipSuccess) e = hipMalloc(&c->diag, sizeof(hf3fs_crc_anomaly));
+    if (e == hipSuccess) e = hipMemcpyAsync(c->tables, host.get(), sizeof(DeviceTables), hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->diag, &none, sizeof(none), hipMemcpyHostToDevice, up);
+    const hipError_t waited = hipStreamSynchronize(up);  // (also after an error: `none` and `host` end here)
+    if (e == hipSuccess) e = waited;
+    (void)hipStreamDestroy(up);
+    if (e != hipSuccess) {
+      if (c->diag) (void)hipFree(c->diag);
+      if (c->tables) (void)hipFree(c->tables);
+      return fail(HF3FS_CRC_DEVICE_ERROR, "context tables: %s", hipGetErrorString(e));
+    }
     (void)options();  // the environment snapshot, once per process
     g_ctx[dev] = std::move(c);
   }

@@ -70,7 +70,10 @@ const char *hf3fs_crc_version(void);
  * shutdown (after which no graph captured earlier may be replayed), or by an
  * uncaptured call once 64 MiB await freeing (hipFree waits for the whole device, so
  * no call pays it routinely; that wait also covers a replay still in flight when its
- * executable graph was destroyed).  Other graphs are never affected.
+ * executable graph was destroyed).  Other graphs are never affected.  A captured
+ * hf3fs_crc_update_batch may be the process's first library call, also in a global-mode capture: what
+ * the library creates for itself (the device context's tables, the update-apply hint
+ * slab, side streams, scratch) is created in relaxed capture mode and is no graph node.
  * release_graph_scratch also frees buffers no graph could take a reference to.
  * graph_scratch_stats: live captured buffers (and their bytes), and those whose graph
  * is gone and that await the next free; any pointer may be NULL. */
