@@ -1,28 +1,26 @@
 // hf3fs_crc_api.hip -- C ABI of libhf3fs_crc.so (declared in include/hf3fs_crc.h).
 //
-// Host side of the boundary: per-device contexts (constant tables in HBM),
-// launch planning and argument validation.  All byte hashing happens in the
+// Host side of the boundary: per-device contexts (constant tables in HBM, built by
+// device_tables.cc; one record per (stream, thread) pair; memory of captured calls in
+// capture_scratch.hip), launch planning and argument validation.  All byte hashing happens in the
 // HIP kernels of crc_kernels.hip; the host only does O(log n) scalar algebra
 // (combine/shift of 32-bit values), exactly like ChecksumInfo::combine does on
 // the reference's host (Common.h:179-198).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <cstdarg>
-#include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
-#include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/hf3fs_crc.h"
 #include "aux_kernels.h"
+#include "capture_scratch.h"
 #include "frame_kernels.h"
 #include "crc_kernels.h"
 #include "digest_kernels.h"
@@ -52,249 +50,50 @@ namespace {
 
 bool valid_type(uint8_t t) { return t == kTypeNone || t == kTypeCrc32c || t == kTypeCrc32; }
 
-void build_short_tables(ShortTables& T, uint32_t poly) {
-  const uint32_t x32 = xpow_bits(32, poly), x8 = xpow_bits(8, poly);
-  for (int k = 0; k < 4; ++k)
-    for (uint32_t b = 0; b < 256; ++b) T.dw[k][b] = gf_mul(b << (8 * k), x32, poly);
-  for (uint32_t b = 0; b < 256; ++b) T.b8[b] = gf_mul(b, x8, poly);
-  for (int n = -kXs8Neg; n < kXs8Pos; ++n) T.xs8[kXs8Neg + n] = xpow_signed_bits(8ll * n, poly);
-}
-
-void build_fold_tables(FoldTables& T, uint32_t poly) {
-  const uint32_t c0 = xpow_neg_bits(32, poly), ch = xpow_neg_bits(4096, poly);
-  for (int j = 0; j < 8; ++j)
-    for (uint32_t n = 0; n < 16; ++n) {
-      const uint32_t a = n << (4 * j);
-      for (int c = 0; c < 32; ++c) T.w[j][n][c] = gf_mul(a, xpow_neg_bits(128ull * c, poly), poly);
-    }
-  for (int k = 0; k < 4; ++k)
-    for (uint32_t b = 0; b < 256; ++b) {
-      T.c0[k][b] = gf_mul(b << (8 * k), c0, poly);
-      T.ch[k][b] = gf_mul(b << (8 * k), ch, poly);
-    }
-}
-
-void build_poly_tables(PolyTables& T, uint32_t poly) {
-  const uint32_t k = xpow_bits(8ull * kBlockBytes, poly);
-  for (int b = 0; b < 4; ++b)
-    for (uint32_t i = 0; i < 256; ++i) T.step[b][i] = gf_mul(i << (8 * b), k, poly);
-  T.xpow[0] = kOne >> 1;
-  T.xinv[0] = x_inverse(poly);
-  for (int i = 1; i < 64; ++i) {
-    T.xpow[i] = gf_mul(T.xpow[i - 1], T.xpow[i - 1], poly);
-    T.xinv[i] = gf_mul(T.xinv[i - 1], T.xinv[i - 1], poly);
-  }
-  for (int t = 0; t < kMulcTables; ++t) {
-    const uint32_t c = xpow_neg_bits(t == 0 ? 32 : (128ull << (t - 1)), poly);
-    for (int b = 0; b < 4; ++b)
-      for (uint32_t i = 0; i < 256; ++i) T.mulc[t][b][i] = gf_mul(i << (8 * b), c, poly);
-  }
-  for (int p = 0; p < 16; ++p) T.xneg8[p] = xpow_neg_bits(8ull * p, poly);
-  for (int p = 0; p < 16; ++p)
-    for (int i = 0; i < 32; ++i) T.xneg8_cols[p][i] = gf_mul(T.xneg8[p], xpow_bits((uint64_t)i, poly), poly);
-  for (int p = 0; p < 4; ++p) T.xpos8[p] = xpow_bits(8ull * p, poly);
-
-  for (int j = 0; j < kPowDigits; ++j) {  // pow8b[j][d] = (x^(8 * 256^j))^d
-    const uint32_t base = xpow_bits(8ull << (8 * j), poly), ibase = xpow_neg_bits(8ull << (8 * j), poly);
-    T.pow8b[j][0] = T.inv8b[j][0] = kOne;
-    for (int d = 1; d < 256; ++d) {
-      T.pow8b[j][d] = gf_mul(T.pow8b[j][d - 1], base, poly);
-      T.inv8b[j][d] = gf_mul(T.inv8b[j][d - 1], ibase, poly);
-    }
-  }
-}
-
 // Work queued by one thread on one stream is ordered, so per-(stream, thread)
 // state is reused safely by that pair; no two pairs ever share it (two threads
 // on the null stream, or on one stream handle, interleave their launches).
 using StreamKey = std::pair<hipStream_t, std::thread::id>;
 inline StreamKey stream_key(hipStream_t s) { return {s, std::this_thread::get_id()}; }
 
-// Device memory the library owns, from hipMalloc also while the calling thread's
-// stream is being captured: the thread switches to relaxed capture mode for the
-// call (hipThreadExchangeStreamCaptureMode), so the allocation is no graph node
-// and invalidates no capture.  Library scratch never comes from the stream-ordered
-// pool.
-hipError_t owned_malloc(void** p, size_t bytes, bool capturing) {
-  if (!capturing) return hipMalloc(p, bytes);
-  hipStreamCaptureMode m = hipStreamCaptureModeRelaxed;
-  hipError_t e = hipThreadExchangeStreamCaptureMode(&m);
-  if (e != hipSuccess) return e;
-  e = hipMalloc(p, bytes);
-  (void)hipThreadExchangeStreamCaptureMode(&m);  // back to the caller's mode
-  return e;
-}
-
-// The calling thread in relaxed capture mode for a scope (back to the caller's mode at its
-// end): what the library allocates or creates for itself inside -- never a graph node -- is
-// neither rejected as capture-unsupported nor invalidates a capture when the call sits inside
-// one (torch.cuda.graph's default mode is global).
-struct RelaxedCapture {
-  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-  hipError_t err;
-  RelaxedCapture() : err(hipThreadExchangeStreamCaptureMode(&mode)) {}
-  ~RelaxedCapture() {
-    if (err == hipSuccess) (void)hipThreadExchangeStreamCaptureMode(&mode);
-  }
-  RelaxedCapture(const RelaxedCapture&) = delete;
-  RelaxedCapture& operator=(const RelaxedCapture&) = delete;
+struct Scratch {
+  uint32_t* ptr = nullptr;
+  size_t words = 0;
+};
+// A side stream with a fork and a join event: the update batch's one-shot apply runs beside
+// the finalize of every verdict.  Per pair, so that two threads capturing
+// graphs never fork into one stream.
+struct Side {
+  hipStream_t side = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+constexpr uint32_t kNoHint = ~0u;
+// Everything the library keeps for one (stream, thread) pair, each member made on first use.
+// Only uncaptured calls use the device memory here: a captured call's belongs to its graph.
+struct PairState {
+  Scratch verify;               // verify values of calls with d_computed == NULL
+  Scratch call;                 // scratch of update / record / frame / digest batches
+  Scratch balance;              // byte-balance region of whole-range launches (bal_words words)
+  uint32_t* counter = nullptr;  // ticket counter: a 16 B slot of a shared slab, not owned
+  uint32_t hint = kNoHint;      // slot of the one-shot apply's pinned hint word
+  Side side;
 };
 
-// ---- Scratch of calls captured into graphs ------------------------------------------
-// Every captured call gets device memory of its own (ticket counter, balance region,
-// verify values, batch scratch), owned by the graph it was captured into.  One owner
-// record per capture sequence (keyed by the capture id): one hipUserObject whose
-// reference the graph holds -- and every executable graph instantiated from it -- and
-// the capture's buffers: requests of <= kCapSmall bytes are carved from kCapSlab-byte
-// slabs of the capture, larger ones get buffers of their own.  When the last reference
-// goes, the destructor moves the buffers to the dead list.  A destructor may not call
-// HIP, so dead buffers are freed by hf3fs_crc_release_graph_scratch, release_stream,
-// shutdown, or by an uncaptured call once the dead list holds >= kCapReapBytes (never
-// in every call: hipFree waits for the whole device).  That device-wide wait of hipFree
-// is also what makes the free safe for an executable graph destroyed while a replay
-// is still in flight (HIP may release user objects at hipGraphExecDestroy without
-// waiting for pending launches).  A capture whose graph could not take the reference
-// (orphan) keeps its buffers until release_graph_scratch or shutdown.  The registry is
-// process-wide (a graph may outlive hf3fs_crc_shutdown) and a heap object that is never
-// destroyed, so a late destructor callback from the HIP runtime's own teardown after
-// this library's static destructors still finds a live mutex and map.  Owners are keyed
-// by a never-reused id (the user object's payload), not by address.
-struct CapturedBuf {
-  void* ptr;
-  int device;
-  size_t bytes;
-};
-struct CaptureOwner {
-  std::vector<CapturedBuf> bufs;
-  unsigned long long cap_id = 0;  // the capture sequence (by_capture key), 0 = none
-  bool orphan = true;
-  uint8_t* slab = nullptr;  // the current slab and its fill
-  size_t slab_used = 0;
-};
-constexpr size_t kCapSmall = 64 << 10, kCapSlab = 256 << 10, kCapReapBytes = 64ull << 20;
-struct CapRegistry {
-  std::mutex mu;
-  std::map<uint64_t, CaptureOwner> live;                  // owner id -> owner
-  std::map<unsigned long long, uint64_t> by_capture;      // capture id -> owner id (capture in progress)
-  std::vector<CapturedBuf> dead;
-  std::atomic<size_t> dead_n{0}, dead_bytes{0};
-  uint64_t next_id = 1;
-};
-CapRegistry& cap_reg() {
-  static CapRegistry* r = new CapRegistry;  // intentionally leaked (late destructor callbacks)
-  return *r;
-}
-
-void captured_graph_gone(void* id) {
-  CapRegistry& R = cap_reg();
-  std::lock_guard<std::mutex> lk(R.mu);
-  auto it = R.live.find((uint64_t)(uintptr_t)id);
-  if (it == R.live.end() || it->second.orphan) return;  // freed already (shutdown), or no graph owns it
-  for (const CapturedBuf& b : it->second.bufs) {
-    R.dead.push_back(b);
-    R.dead_bytes.fetch_add(b.bytes);
+// The end of a pair record that left the context (release_stream, shutdown), never with the
+// context locked: waits for the side stream, destroys it and its events and frees the three
+// buffers (an error of the frees is returned).  The counter and hint slots stay in their slabs.
+hipError_t destroy_pair(const PairState& p) {
+  if (p.side.side) {
+    (void)hipStreamSynchronize(p.side.side);
+    (void)hipEventDestroy(p.side.fork);
+    (void)hipEventDestroy(p.side.join);
+    (void)hipStreamDestroy(p.side.side);
   }
-  auto bc = R.by_capture.find(it->second.cap_id);
-  if (bc != R.by_capture.end() && bc->second == it->first) R.by_capture.erase(bc);
-  R.live.erase(it);
-  R.dead_n.store(R.dead.size());
-}
-
-// hipFree the buffers of destroyed graphs.  Relaxed capture mode for the frees, so that
-// another thread's global-mode capture neither fails this call nor is invalidated by it.
-void free_captured(std::vector<CapturedBuf>& dead) {
-  if (dead.empty()) return;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  hipStreamCaptureMode m = hipStreamCaptureModeRelaxed;
-  (void)hipThreadExchangeStreamCaptureMode(&m);
-  for (const CapturedBuf& b : dead) {
-    (void)hipSetDevice(b.device);
-    (void)hipFree(b.ptr);
-  }
-  (void)hipThreadExchangeStreamCaptureMode(&m);
-  (void)hipSetDevice(prev);
-}
-
-// Free the dead list (force), or from an uncaptured call only once it holds kCapReapBytes.
-void reap_captured(bool force = false) {
-  CapRegistry& R = cap_reg();
-  if (R.dead_n.load(std::memory_order_relaxed) == 0) return;
-  if (!force && R.dead_bytes.load(std::memory_order_relaxed) < kCapReapBytes) return;
-  std::vector<CapturedBuf> dead;
-  {
-    std::lock_guard<std::mutex> lk(R.mu);
-    dead.swap(R.dead);
-    R.dead_n.store(0);
-    R.dead_bytes.store(0);
-  }
-  free_captured(dead);
-}
-
-// `bytes` of device memory for the call being captured on s, owned by the capture's graph.
-hipError_t capture_malloc(int device, hipStream_t s, size_t bytes, void** out) {
-  CapRegistry& R = cap_reg();
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  unsigned long long cap_id = 0;
-  hipGraph_t graph = nullptr;
-  const bool info = hipStreamGetCaptureInfo_v2(s, &st, &cap_id, &graph, nullptr, nullptr) == hipSuccess && graph &&
-                    st == hipStreamCaptureStatusActive;
-  uint64_t id = 0;
-  bool fresh = false;
-  {
-    std::lock_guard<std::mutex> lk(R.mu);
-    auto bc = info ? R.by_capture.find(cap_id) : R.by_capture.end();
-    auto ow = bc != R.by_capture.end() ? R.live.find(bc->second) : R.live.end();
-    if (ow == R.live.end() || ow->second.bufs.empty() || ow->second.bufs.front().device != device) {
-      id = R.next_id++;
-      R.live[id].cap_id = info ? cap_id : 0;  // an orphan until its graph holds the reference
-      if (info) R.by_capture[cap_id] = id;
-      fresh = true;
-    } else {
-      id = ow->first;
-    }
-  }
-  if (fresh && info) {  // the owner's user object, retained by the graph
-    hipUserObject_t obj = nullptr;
-    if (hipUserObjectCreate(&obj, (void*)(uintptr_t)id, captured_graph_gone, 1, hipUserObjectNoDestructorSync) ==
-        hipSuccess) {
-      {  // owned before the graph holds the reference: the destructor may run as soon as it does
-        std::lock_guard<std::mutex> lk(R.mu);
-        R.live[id].orphan = false;
-      }
-      if (hipGraphRetainUserObject(graph, obj, 1, hipGraphUserObjectMove) != hipSuccess) {
-        {
-          std::lock_guard<std::mutex> lk(R.mu);
-          R.live[id].orphan = true;  // the release below then frees nothing
-        }
-        (void)hipUserObjectRelease(obj, 1);
-      }
-    }
-  }
-  std::lock_guard<std::mutex> lk(R.mu);
-  auto it = R.live.find(id);
-  if (it == R.live.end()) return hipErrorInvalidValue;  // (the graph died during this call)
-  CaptureOwner& o = it->second;
-  const size_t need = (bytes + 255) & ~size_t(255);
-  if (need <= kCapSmall) {
-    if (!o.slab || o.slab_used + need > kCapSlab) {
-      void* p = nullptr;
-      hipError_t e = owned_malloc(&p, kCapSlab, true);
-      if (e != hipSuccess) return e;
-      o.bufs.push_back(CapturedBuf{p, device, kCapSlab});
-      o.slab = (uint8_t*)p;
-      o.slab_used = 0;
-    }
-    *out = o.slab + o.slab_used;
-    o.slab_used += need;
-    return hipSuccess;
-  }
-  void* p = nullptr;
-  hipError_t e = owned_malloc(&p, bytes, true);
-  if (e != hipSuccess) return e;
-  o.bufs.push_back(CapturedBuf{p, device, bytes});
-  *out = p;
-  return hipSuccess;
+  hipError_t err = hipSuccess;
+  for (const Scratch* b : {&p.verify, &p.call, &p.balance})
+    if (b->ptr)
+      if (const hipError_t e = hipFree(b->ptr)) err = e;
+  return err;
 }
 
 struct Context {
@@ -303,75 +102,26 @@ struct Context {
   DeviceTables* tables = nullptr;  // device
   hf3fs_crc_anomaly* diag = nullptr;  // device: the self-check's record (hf3fs_crc_anomalies)
   std::mutex mu;                   // guards everything below
-  // verify scratch (d_computed == NULL), per (stream, calling thread)
-  struct Scratch {
-    uint32_t* ptr = nullptr;
-    size_t words = 0;
-  };
-  std::map<StreamKey, Scratch> scratch;
-  // scratch of update / record / frame / digest batches, per (stream, calling thread)
-  std::map<StreamKey, Scratch> call;
+  std::map<StreamKey, PairState> pairs;
   // Ticket counters of the dynamic task queues (16 B each, zeroed on the launch
   // stream right before the launch).  A (stream, thread) pair owns one counter
-  // for all its launches (they are stream-ordered), a slot of a slab.  A launch
-  // captured into a graph gets a counter of its own, owned by the graph
-  // (capture_malloc), since the graph may be replayed on any stream.
+  // for all its launches (they are stream-ordered), a slot of a slab.
   static constexpr uint32_t kSlabSlots = 16384;
   std::vector<uint32_t*> slabs;
   uint32_t slab_used = kSlabSlots;
-  std::map<StreamKey, uint32_t*> counters;
-  int queue_counter(hipStream_t s, uint32_t** out) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_OR_FAIL(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone) {
-      HIP_OR_FAIL(capture_malloc(device, s, 16, (void**)out));
-      return HF3FS_CRC_OK;
-    }
-    reap_captured();
-    std::lock_guard<std::mutex> lk(mu);
-    uint32_t*& q = counters[stream_key(s)];
-    if (!q) {
-      if (slab_used == kSlabSlots) {
-        uint32_t* slab = nullptr;
-        HIP_OR_FAIL(hipMalloc(&slab, kSlabSlots * 16));
-        slabs.push_back(slab);
-        slab_used = 0;
-      }
-      q = slabs.back() + 4 * slab_used++;
-    }
-    *out = q;
-    return HF3FS_CRC_OK;
-  }
-  // Byte-balance scratch of whole-range launches (partial sums + per-wave task
-  // boundaries, bal_words words): one per (stream, thread) pair, and for a
-  // launch captured into a graph a region owned by the graph (capture_malloc).
+  // Byte-balance scratch of whole-range launches: partial sums + per-wave task boundaries.
   static constexpr uint32_t kBalBlocksMax = 1024;
-  std::map<StreamKey, uint32_t*> bal_scratch;
   size_t bal_words() const { return (2 * kBalBlocksMax + (size_t)cus * kWaves + 1 + 63) / 64 * 64; }
-  int balance_scratch(hipStream_t s, uint32_t** out) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_OR_FAIL(hipStreamIsCapturing(s, &cs));
-    *out = nullptr;
-    if (cs != hipStreamCaptureStatusNone) {
-      HIP_OR_FAIL(capture_malloc(device, s, bal_words() * 4, (void**)out));
-      return HF3FS_CRC_OK;
-    }
-    reap_captured();
-    std::lock_guard<std::mutex> lk(mu);
-    uint32_t*& q = bal_scratch[stream_key(s)];
-    if (!q) HIP_OR_FAIL(hipMalloc(&q, bal_words() * 4));
-    *out = q;
-    return HF3FS_CRC_OK;
-  }
   // One-shot apply grid hints (update_batch): a pinned word per (stream, thread) pair where the
   // apply kernel leaves (pieces << 32 | n) of its call; the pair's next call sizes its one-shot
   // grid from it.  One slab for the process's pairs (a word of a captured call's graph stays
   // valid until shutdown); more pairs than slots share words (only the grid's fit suffers).
-  // release_stream returns the stream's slots to a free list.
+  // hint_uses counts the live pairs of a slot: release_stream puts a slot on the free list
+  // when its last pair goes.
   static constexpr uint32_t kHintSlots = 4096;
   uint64_t* hint_host = nullptr;
   uint64_t* hint_dev = nullptr;
-  std::map<StreamKey, uint32_t> hint_slot;
+  uint32_t hint_uses[kHintSlots] = {};
   std::vector<uint32_t> hint_free;
   uint32_t hint_next = 0;
   int hint_word(hipStream_t s, uint64_t** host, uint64_t** dev) {
@@ -383,46 +133,36 @@ struct Context {
       memset(hint_host, 0, kHintSlots * 8);
       HIP_OR_FAIL(hipHostGetDevicePointer((void**)&hint_dev, hint_host, 0));
     }
-    auto it = hint_slot.find(stream_key(s));
-    if (it == hint_slot.end()) {
-      uint32_t slot;
+    uint32_t& slot = pairs[stream_key(s)].hint;
+    if (slot == kNoHint) {
       if (!hint_free.empty()) {
         slot = hint_free.back();
         hint_free.pop_back();
       } else {
         slot = hint_next++ % kHintSlots;
       }
-      it = hint_slot.emplace(stream_key(s), slot).first;
+      ++hint_uses[slot];
     }
-    *host = hint_host + it->second;
-    *dev = hint_dev + it->second;
+    *host = hint_host + slot;
+    *dev = hint_dev + slot;
     return HF3FS_CRC_OK;
   }
-  // A side stream per (stream, thread) pair with a fork and a join event: the update batch's
-  // one-shot apply runs beside the finalize of every verdict.  Per pair, so
-  // that two threads capturing graphs never fork into one stream; created in relaxed capture
-  // mode (a call may be captured), destroyed by release_stream and shutdown.
-  struct Side {
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-  };
-  std::map<StreamKey, Side> sides;
+  // The pair's side stream, created in relaxed capture mode (a call may be captured).
   int side_of(hipStream_t s, Side* out) {
     {
       std::lock_guard<std::mutex> lk(mu);
-      auto it = sides.find(stream_key(s));
-      if (it != sides.end()) {
-        *out = it->second;
-        return HF3FS_CRC_OK;
-      }
+      *out = pairs[stream_key(s)].side;
     }
+    if (out->side) return HF3FS_CRC_OK;
     Side n;
-    hipStreamCaptureMode m = hipStreamCaptureModeRelaxed;
-    HIP_OR_FAIL(hipThreadExchangeStreamCaptureMode(&m));
-    hipError_t e = hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&n.fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&n.join, hipEventDisableTiming);
-    (void)hipThreadExchangeStreamCaptureMode(&m);
+    hipError_t e;
+    {
+      RelaxedCapture relaxed;
+      e = relaxed.err;
+      if (e == hipSuccess) e = hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&n.fork, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&n.join, hipEventDisableTiming);
+    }
     if (e != hipSuccess) {
       if (n.join) (void)hipEventDestroy(n.join);
       if (n.fork) (void)hipEventDestroy(n.fork);
@@ -430,15 +170,9 @@ struct Context {
       return fail(HF3FS_CRC_DEVICE_ERROR, "side stream: %s", hipGetErrorString(e));
     }
     std::lock_guard<std::mutex> lk(mu);
-    sides[stream_key(s)] = n;
+    pairs[stream_key(s)].side = n;
     *out = n;
     return HF3FS_CRC_OK;
-  }
-  static void destroy_side(const Side& x) {
-    (void)hipStreamSynchronize(x.side);
-    (void)hipEventDestroy(x.fork);
-    (void)hipEventDestroy(x.join);
-    (void)hipStreamDestroy(x.side);
   }
   // host staging (hf3fs_crc_create_host), one caller at a time
   std::mutex stage_mu;
@@ -463,12 +197,7 @@ int get_context(Context** out) {
     c->device = dev;
     HIP_OR_FAIL(hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, dev));
     auto host = std::make_unique<DeviceTables>();
-    build_poly_tables(host->poly[0], kPolyCrc32c);
-    build_poly_tables(host->poly[1], kPolyCrc32);
-    build_short_tables(host->sh[0], kPolyCrc32c);
-    build_short_tables(host->sh[1], kPolyCrc32);
-    build_fold_tables(host->fold[0], kPolyCrc32c);
-    build_fold_tables(host->fold[1], kPolyCrc32);
+    build_device_tables(*host);
     // The process's first library call may sit inside a stream capture: the allocations in
     // relaxed capture mode, the uploads on a stream of their own and waited for there (nothing
     // touches the null stream or the capturing one).
@@ -494,6 +223,103 @@ int get_context(Context** out) {
   }
   *out = g_ctx[dev].get();
   return HF3FS_CRC_OK;
+}
+
+// Is the call on s being captured into a graph?
+int is_capturing(hipStream_t s, bool* capturing) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_OR_FAIL(hipStreamIsCapturing(s, &cs));
+  *capturing = cs != hipStreamCaptureStatusNone;
+  return HF3FS_CRC_OK;
+}
+
+// The calling (stream, thread) pair's buffer `member`, at least `words` long (roomy: sized
+// up to a multiple of 64 Ki words and at least doubled, else exactly `words`).  Only that
+// pair ever uses the buffer and only this thread launched work on it, all of it on s, so
+// growth detaches it under the lock and waits for the stream, frees and allocates with the
+// lock released (other threads' calls never wait for this stream; not graph-capturable, a
+// warm-up call of the largest size avoids it), then publishes the new buffer.  On a failure
+// before the new buffer exists the old one goes back into the record (nothing leaks).
+int pair_buffer(Context* c, Scratch PairState::*member, hipStream_t s, size_t words, bool roomy, uint32_t** out) {
+  const StreamKey key = stream_key(s);
+  Scratch e;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    Scratch& slot = c->pairs[key].*member;
+    e = slot;
+    if (slot.words < words) slot = Scratch{};
+  }
+  if (e.words < words) {
+    const size_t grow_to = roomy ? std::max<size_t>((words + 65535) / 65536 * 65536, 2 * e.words) : words;
+    hipError_t err = e.ptr ? hipStreamSynchronize(s) : hipSuccess;
+    if (err == hipSuccess && e.ptr) {
+      err = hipFree(e.ptr);
+      if (err == hipSuccess) e = Scratch{};
+    }
+    uint32_t* fresh = nullptr;
+    if (err == hipSuccess) err = hipMalloc(&fresh, grow_to * sizeof(uint32_t));
+    if (err == hipSuccess) e = Scratch{fresh, grow_to};
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->pairs[key].*member = e;  // the new buffer, or after a failure the old one (none, if it was freed)
+    if (err != hipSuccess)
+      return fail(HF3FS_CRC_DEVICE_ERROR, "scratch growth to %zu words: %s", grow_to, hipGetErrorString(err));
+  }
+  *out = e.ptr;
+  return HF3FS_CRC_OK;
+}
+
+// The pair's ticket counter: a slot carved from the context's slabs on first use.
+int pair_counter(Context* c, hipStream_t s, uint32_t** out) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  uint32_t*& q = c->pairs[stream_key(s)].counter;
+  if (!q) {
+    if (c->slab_used == Context::kSlabSlots) {
+      uint32_t* slab = nullptr;
+      HIP_OR_FAIL(hipMalloc(&slab, Context::kSlabSlots * 16));
+      c->slabs.push_back(slab);
+      c->slab_used = 0;
+    }
+    q = c->slabs.back() + 4 * c->slab_used++;
+  }
+  *out = q;
+  return HF3FS_CRC_OK;
+}
+
+// Device memory of one call on s: library-owned hipMalloc memory, never the stream-ordered
+// pool (rounds 1 and 3 saw the first DELTA update of a process -- the first call whose
+// per-call hipMallocAsync scratch the pool had to grow -- verify a correct payload as
+// mismatched in 2-3 of 16 fresh processes, and a retry pass).  Outside a
+// stream capture it is the calling (stream, thread) pair's persistent member.  During a
+// capture it is memory of the captured call alone, owned by the captured graph and freed
+// after the graph is gone (capture_malloc): the graph may be replayed on any stream, and a
+// replay never touches pair memory that release_stream or a later growth freed.
+// Option poison (test only): the words of a verify or call buffer are first filled with that
+// pattern on the stream, so a call that read a word before writing it would see junk
+// (tests/test_gpu_parity.py::test_update_batch_poisoned_scratch).
+enum class Mem { kVerify, kCall, kBalance, kCounter };
+int call_memory(Context* c, hipStream_t s, Mem what, size_t words, uint32_t** out) {
+  bool capturing = false;
+  if (int rc = is_capturing(s, &capturing)) return rc;
+  if (capturing) {
+    HIP_OR_FAIL(capture_malloc(c->device, s, words * 4, (void**)out));
+  } else {
+    reap_captured();
+    Scratch PairState::*const buffer[] = {&PairState::verify, &PairState::call, &PairState::balance};
+    const int rc = what == Mem::kCounter ? pair_counter(c, s, out)
+                                         : pair_buffer(c, buffer[(int)what], s, words, what == Mem::kCall, out);
+    if (rc) return rc;
+  }
+  if (what == Mem::kVerify || what == Mem::kCall)
+    if (const uint32_t pattern = options().poison.load()) HIP_OR_FAIL(launch_fill_words(*out, words, pattern, s));
+  return HF3FS_CRC_OK;
+}
+
+// Scratch of one batch call (update, record jobs, frames, file digest).
+int call_scratch(Context* c, hipStream_t s, size_t bytes, void** out) {
+  uint32_t* p = nullptr;
+  const int rc = call_memory(c, s, Mem::kCall, (bytes + 3) / 4, &p);
+  *out = p;
+  return rc;
 }
 
 // Cross-task head prefetch for whole-buffer tasks on a static stride (DESIGN.md
@@ -552,7 +378,7 @@ int launch_prepare(Context* c, Plan& p, uint64_t n, uint32_t* out, hipStream_t s
   if (p.segs > 1 || p.dyn_max) HIP_OR_FAIL(launch_zero_words(out, n, s));
   p.queue = nullptr;
   if ((tasks > (uint64_t)p.grid * kWaves || p.dyn_max) && tickets_allowed()) {
-    if (int rc = c->queue_counter(s, &p.queue)) return rc;
+    if (int rc = call_memory(c, s, Mem::kCounter, 4, &p.queue)) return rc;
     HIP_OR_FAIL(launch_zero_counter(p.queue, s));
   }
   return HF3FS_CRC_OK;
@@ -569,8 +395,7 @@ int plan_balance(Context* c, Plan& p, const Src& src, uint64_t n, uint64_t max_l
   // (the kernel drops its ticket queue for more than 16 tasks per wave)
   if (!on || p.segs != 1 || p.dyn_max || max_len <= p.pipe_max || n <= 16 * nw) return HF3FS_CRC_OK;
   uint32_t* sc = nullptr;
-  if (int rc = c->balance_scratch(s, &sc)) return rc;
-  if (!sc) return HF3FS_CRC_OK;
+  if (int rc = call_memory(c, s, Mem::kBalance, c->bal_words(), &sc)) return rc;
   const uint32_t nblocks = (uint32_t)std::min<uint64_t>(Context::kBalBlocksMax, std::max<uint64_t>(1, n / 1024));
   uint64_t* partial = (uint64_t*)sc;
   uint32_t* bal = sc + 2 * Context::kBalBlocksMax;
@@ -625,100 +450,6 @@ int run_ranges_list(Context* c, uint8_t type, const ListSource& src, uint64_t ma
   return HF3FS_CRC_OK;
 }
 
-// The verify scratch of the calling thread on stream s.  Growth waits for the
-// stream's queued work before freeing the old buffer (not graph-capturable
-// then; a warm-up call of the largest size avoids it).  Only this thread ever
-// launched work reading the old buffer, all of it on s.
-// The calling (stream, thread) pair's buffer in `table`, at least `words` long.
-// Only that pair ever uses the entry, so growth detaches it under the lock and
-// waits for the stream, frees and allocates with the lock released (other
-// threads' calls never wait for this stream), then publishes the new buffer.
-// Option poison (test only): the words handed out are first filled with that
-// pattern on the stream, so a call that read a word before writing it would
-// see junk (tests/test_gpu_parity.py::test_update_batch_poisoned_scratch).
-int pair_buffer(Context* c, std::map<StreamKey, Context::Scratch> Context::*table, hipStream_t s, size_t words,
-                size_t grow_to, uint32_t** out) {
-  const StreamKey key = stream_key(s);
-  Context::Scratch e;
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    Context::Scratch& slot = (c->*table)[key];
-    if (slot.words >= words) {
-      e = slot;
-    } else {
-      e = slot;
-      slot = Context::Scratch{};
-    }
-  }
-  if (e.words < words) {
-    // only this thread launched work on the old buffer, all of it on s.  On a failure
-    // before the new buffer exists the old entry goes back into the slot (nothing leaks).
-    hipError_t err = e.ptr ? hipStreamSynchronize(s) : hipSuccess;
-    if (err == hipSuccess && e.ptr) {
-      err = hipFree(e.ptr);
-      if (err == hipSuccess) e = Context::Scratch{};
-    }
-    uint32_t* fresh = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&fresh, grow_to * sizeof(uint32_t));
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (err != hipSuccess) {
-      (c->*table)[key] = e;  // the old buffer (or none, if it was freed)
-      return fail(HF3FS_CRC_DEVICE_ERROR, "scratch growth to %zu words: %s", grow_to, hipGetErrorString(err));
-    }
-    e = Context::Scratch{fresh, grow_to};
-    (c->*table)[key] = e;
-  }
-  if (const uint32_t pattern = options().poison.load()) HIP_OR_FAIL(launch_fill_words(e.ptr, words, pattern, s));
-  *out = e.ptr;
-  return HF3FS_CRC_OK;
-}
-
-// The verify values of a call with d_computed == NULL: the calling (stream, thread)
-// pair's buffer, or during a capture a buffer owned by the captured graph (so a
-// replay never writes a pair buffer that release_stream or a later growth freed).
-int stream_scratch(Context* c, hipStream_t s, size_t words, uint32_t** out) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  HIP_OR_FAIL(hipStreamIsCapturing(s, &cs));
-  if (cs != hipStreamCaptureStatusNone) {
-    HIP_OR_FAIL(capture_malloc(c->device, s, words * 4, (void**)out));
-    if (const uint32_t pattern = options().poison.load()) HIP_OR_FAIL(launch_fill_words(*out, words, pattern, s));
-    return HF3FS_CRC_OK;
-  }
-  reap_captured();
-  return pair_buffer(c, &Context::scratch, s, words, words, out);
-}
-
-// Scratch of one batch call (update, record jobs, frames, file digest): library-
-// owned hipMalloc memory, never the stream-ordered pool.  Outside a stream capture
-// it is the calling (stream, thread) pair's persistent buffer (pair_buffer).
-// During a capture it is a buffer of the captured call alone, owned by the captured
-// graph and freed after the graph is gone (capture_malloc).  Rounds 1 and 3
-// saw the first DELTA update of a process -- the first call whose per-call
-// hipMallocAsync scratch the pool had to grow -- verify a correct payload as
-// mismatched in 2-3 of 16 fresh processes, and a retry pass.
-int call_scratch(Context* c, hipStream_t s, size_t bytes, void** out) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  HIP_OR_FAIL(hipStreamIsCapturing(s, &cs));
-  const size_t words = (bytes + 3) / 4;
-  if (cs != hipStreamCaptureStatusNone) {
-    HIP_OR_FAIL(capture_malloc(c->device, s, words * 4, out));
-    if (const uint32_t pattern = options().poison.load()) HIP_OR_FAIL(launch_fill_words(*out, words, pattern, s));
-    return HF3FS_CRC_OK;
-  }
-  reap_captured();
-  uint32_t* p = nullptr;
-  std::size_t have = 0;
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->call.find(stream_key(s));
-    if (it != c->call.end()) have = it->second.words;
-  }
-  const size_t grow_to = std::max<size_t>((words + 65535) / 65536 * 65536, 2 * have);
-  if (int rc = pair_buffer(c, &Context::call, s, words, grow_to, &p)) return rc;
-  *out = p;
-  return HF3FS_CRC_OK;
-}
-
 // prep -> k_crc_ranges -> finalize over per-record jobs, with stream-ordered
 // scratch {maxl[4], addr[n], len[n], v[n]}: the shape shared by the record
 // batches (read results, scrub, frames).
@@ -770,6 +501,9 @@ int run_record_jobs(Context* c, uint8_t type, uint64_t n, uint32_t max_len, uint
   return rc;
 }
 
+int create_host_staged(Context* c, uint8_t type, const void* const* h_bufs, const uint64_t* h_lens,
+                       const uint32_t* h_starts, uint32_t* h_out, uint64_t n);  // (below hf3fs_crc_create_host)
+
 }  // namespace
 
 int hf3fs_crc::current_tables(const DeviceTables** out) {
@@ -799,18 +533,16 @@ void hf3fs_crc_shutdown(void) {
   for (auto& c : g_ctx) {
     if (!c) continue;
     (void)hipSetDevice(c->device);
+    std::map<StreamKey, PairState> gone;
+    {
+      std::lock_guard<std::mutex> lk2(c->mu);
+      gone.swap(c->pairs);
+    }
+    for (auto& kv : gone) (void)destroy_pair(kv.second);
     (void)hipFree(c->tables);
     for (uint32_t* slab : c->slabs) (void)hipFree(slab);
-    for (auto& kv : c->scratch)
-      if (kv.second.ptr) (void)hipFree(kv.second.ptr);
-    for (auto& kv : c->call)
-      if (kv.second.ptr) (void)hipFree(kv.second.ptr);
     (void)hipFree(c->diag);
     if (c->hint_host) (void)hipHostFree(c->hint_host);
-    for (auto& kv : c->sides) Context::destroy_side(kv.second);
-    c->sides.clear();
-    for (auto& kv : c->bal_scratch)
-      if (kv.second) (void)hipFree(kv.second);
     for (int k = 0; k < 2; ++k) {
       if (c->pinned[k]) (void)hipHostFree(c->pinned[k]);
       if (c->pdesc[k]) (void)hipHostFree(c->pdesc[k]);
@@ -820,19 +552,7 @@ void hf3fs_crc_shutdown(void) {
     }
   }
   g_ctx.clear();
-  // every captured call's buffers: graphs still alive after shutdown must not be replayed
-  std::vector<CapturedBuf> all;
-  {
-    CapRegistry& R = cap_reg();
-    std::lock_guard<std::mutex> lk2(R.mu);
-    all.swap(R.dead);
-    for (auto& kv : R.live) all.insert(all.end(), kv.second.bufs.begin(), kv.second.bufs.end());
-    R.live.clear();
-    R.by_capture.clear();
-    R.dead_n.store(0);
-    R.dead_bytes.store(0);
-  }
-  free_captured(all);
+  free_all_captured();
 }
 
 int hf3fs_crc_release_stream(void* stream) {
@@ -841,87 +561,28 @@ int hf3fs_crc_release_stream(void* stream) {
   hipStream_t s = (hipStream_t)stream;
   HIP_OR_FAIL(hipStreamSynchronize(s));
   reap_captured(true);
-  std::vector<void*> dead;
+  std::vector<PairState> gone;
   {
     std::lock_guard<std::mutex> lk(c->mu);
-    for (auto* table : {&c->scratch, &c->call})
-      for (auto it = table->begin(); it != table->end();) {
-        if (it->first.first == s) {
-          dead.push_back(it->second.ptr);
-          it = table->erase(it);
-        } else {
-          ++it;
-        }
-      }
-    for (auto it = c->bal_scratch.begin(); it != c->bal_scratch.end();) {
-      if (it->first.first == s) {
-        dead.push_back(it->second);
-        it = c->bal_scratch.erase(it);
-      } else {
+    for (auto it = c->pairs.begin(); it != c->pairs.end();) {
+      if (it->first.first != s) {
         ++it;
+        continue;
       }
-    }
-    // ticket counters are 16 B slots of shared slabs: the stream's slot is dropped, not freed
-    for (auto it = c->counters.begin(); it != c->counters.end();) it = it->first.first == s ? c->counters.erase(it) : ++it;
-    for (auto it = c->sides.begin(); it != c->sides.end();) {
-      if (it->first.first == s) {
-        Context::destroy_side(it->second);
-        it = c->sides.erase(it);
-      } else {
-        ++it;
+      // the pair's one-shot hint word: cleared (the slot's next call starts with the ticketed
+      // apply that counts its pieces), the slot back on the free list with its last pair
+      if (const uint32_t slot = it->second.hint; slot != kNoHint) {
+        __atomic_store_n(c->hint_host + slot, 0ull, __ATOMIC_RELEASE);
+        if (--c->hint_uses[slot] == 0) c->hint_free.push_back(slot);
       }
-    }
-    // the stream's one-shot hint words: cleared (the slot's next pair starts with the ticketed
-    // call that counts its pieces) and back on the free list
-    for (auto it = c->hint_slot.begin(); it != c->hint_slot.end();) {
-      if (it->first.first == s) {
-        __atomic_store_n(c->hint_host + it->second, 0ull, __ATOMIC_RELEASE);
-        c->hint_free.push_back(it->second);
-        it = c->hint_slot.erase(it);
-      } else {
-        ++it;
-      }
+      gone.push_back(it->second);
+      it = c->pairs.erase(it);
     }
   }
-  for (void* p : dead)
-    if (p) HIP_OR_FAIL(hipFree(p));
-  return HF3FS_CRC_OK;
-}
-
-int hf3fs_crc_release_graph_scratch(void) {
-  reap_captured(true);  // buffers of graphs already destroyed
-  std::vector<CapturedBuf> orphans;
-  {
-    CapRegistry& R = cap_reg();
-    std::lock_guard<std::mutex> lk(R.mu);
-    for (auto it = R.live.begin(); it != R.live.end();) {
-      if (it->second.orphan) {
-        orphans.insert(orphans.end(), it->second.bufs.begin(), it->second.bufs.end());
-        it = R.live.erase(it);
-      } else {
-        ++it;
-      }
-    }
-    // finished captures: no later allocation joins them
-    for (auto it = R.by_capture.begin(); it != R.by_capture.end();)
-      it = R.live.count(it->second) ? ++it : R.by_capture.erase(it);
-  }
-  free_captured(orphans);
-  return HF3FS_CRC_OK;
-}
-
-int hf3fs_crc_graph_scratch_stats(uint64_t* live_buffers, uint64_t* live_bytes, uint64_t* dead_buffers) {
-  CapRegistry& R = cap_reg();
-  std::lock_guard<std::mutex> lk(R.mu);
-  uint64_t bytes = 0, n = 0;
-  for (auto& kv : R.live)
-    for (const CapturedBuf& b : kv.second.bufs) {
-      bytes += b.bytes;
-      ++n;
-    }
-  if (live_buffers) *live_buffers = n;
-  if (live_bytes) *live_bytes = bytes;
-  if (dead_buffers) *dead_buffers = R.dead.size();
+  hipError_t err = hipSuccess;
+  for (const PairState& p : gone)
+    if (const hipError_t e = destroy_pair(p)) err = e;
+  HIP_OR_FAIL(err);
   return HF3FS_CRC_OK;
 }
 
@@ -1054,74 +715,65 @@ int hf3fs_crc_create_strided(uint8_t type, const void* d_base, uint64_t stride, 
   return HF3FS_CRC_OK;
 }
 
-static int verify_tail(Context* c, const uint32_t* computed, const uint32_t* d_expected, uint8_t* d_mismatch,
-                       uint32_t* d_count, uint64_t n, hipStream_t s) {
+// The opening of the three verify entry points: validation, the context, and where the
+// computed values go (d_computed, else library memory of the call).  *comp stays null for
+// n == 0 (the count is zeroed: nothing more to do).
+static int verify_begin(uint8_t type, bool args_ok, uint32_t* d_count, uint32_t* d_computed, uint64_t n, hipStream_t s,
+                        Context** c, uint32_t** comp) {
+  *comp = nullptr;
+  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
+  if (!d_count) return fail(HF3FS_CRC_INVALID_ARG, "null mismatch count");
+  if (n == 0) {
+    HIP_OR_FAIL(launch_zero_words(d_count, 1, s));
+    return HF3FS_CRC_OK;
+  }
+  if (!args_ok) return fail(HF3FS_CRC_INVALID_ARG, "null argument");
+  if (int rc = get_context(c)) return rc;
+  *comp = d_computed;
+  return d_computed ? HF3FS_CRC_OK : call_memory(*c, s, Mem::kVerify, n, comp);
+}
+
+static int verify_tail(const uint32_t* computed, const uint32_t* d_expected, uint8_t* d_mismatch, uint32_t* d_count,
+                       uint64_t n, hipStream_t s) {
   HIP_OR_FAIL(launch_zero_words(d_count, 1, s));
   HIP_OR_FAIL(launch_compare(computed, d_expected, d_mismatch, d_count, n, s));
-  (void)c;
   return HF3FS_CRC_OK;
 }
 
 int hf3fs_crc_verify_batch(uint8_t type, const void* const* d_bufs, const uint64_t* d_lens,
                            const uint32_t* d_expected, uint8_t* d_mismatch, uint32_t* d_mismatch_count,
                            uint32_t* d_computed, uint64_t n, uint64_t max_len, void* stream) {
-  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
-  if (!d_mismatch_count) return fail(HF3FS_CRC_INVALID_ARG, "null mismatch count");
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
-    HIP_OR_FAIL(launch_zero_words(d_mismatch_count, 1, s));
-    return HF3FS_CRC_OK;
-  }
-  if (!d_expected || !d_mismatch) return fail(HF3FS_CRC_INVALID_ARG, "null argument");
   Context* c = nullptr;
-  if (int rc = get_context(&c)) return rc;
-  uint32_t* comp = d_computed;
-  if (!comp) {
-    if (int rc = stream_scratch(c, s, n, &comp)) return rc;
-  }
+  uint32_t* comp = nullptr;
+  if (const int rc = verify_begin(type, d_expected && d_mismatch, d_mismatch_count, d_computed, n, s, &c, &comp);
+      rc || !comp)
+    return rc;
   if (int rc = hf3fs_crc_create_batch(type, d_bufs, d_lens, nullptr, comp, n, max_len, stream)) return rc;
-  return verify_tail(c, comp, d_expected, d_mismatch, d_mismatch_count, n, s);
+  return verify_tail(comp, d_expected, d_mismatch, d_mismatch_count, n, s);
 }
 
 int hf3fs_crc_verify_strided(uint8_t type, const void* d_base, uint64_t stride, uint64_t len, uint64_t n,
                              const uint32_t* d_expected, uint8_t* d_mismatch, uint32_t* d_mismatch_count,
                              uint32_t* d_computed, void* stream) {
-  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
-  if (!d_mismatch_count) return fail(HF3FS_CRC_INVALID_ARG, "null mismatch count");
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
-    HIP_OR_FAIL(launch_zero_words(d_mismatch_count, 1, s));
-    return HF3FS_CRC_OK;
-  }
-  if (!d_expected || !d_mismatch) return fail(HF3FS_CRC_INVALID_ARG, "null argument");
   Context* c = nullptr;
-  if (int rc = get_context(&c)) return rc;
-  uint32_t* comp = d_computed;
-  if (!comp) {
-    if (int rc = stream_scratch(c, s, n, &comp)) return rc;
-  }
+  uint32_t* comp = nullptr;
+  if (const int rc = verify_begin(type, d_expected && d_mismatch, d_mismatch_count, d_computed, n, s, &c, &comp);
+      rc || !comp)
+    return rc;
   if (int rc = hf3fs_crc_create_strided(type, d_base, stride, len, n, ~0u, comp, stream)) return rc;
-  return verify_tail(c, comp, d_expected, d_mismatch, d_mismatch_count, n, s);
+  return verify_tail(comp, d_expected, d_mismatch, d_mismatch_count, n, s);
 }
 
 int hf3fs_crc_verify_blocks(uint8_t type, const void* d_arena, const uint64_t* d_offsets, const uint32_t* d_lens,
                             const uint32_t* d_expected, uint8_t* d_mismatch, uint32_t* d_mismatch_count,
                             uint32_t* d_computed, uint64_t n, uint32_t max_len, void* stream) {
-  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
-  if (!d_mismatch_count) return fail(HF3FS_CRC_INVALID_ARG, "null mismatch count");
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
-    HIP_OR_FAIL(launch_zero_words(d_mismatch_count, 1, s));
-    return HF3FS_CRC_OK;
-  }
-  if (!d_arena || !d_offsets || !d_lens || !d_expected || !d_mismatch)
-    return fail(HF3FS_CRC_INVALID_ARG, "null argument");
   Context* c = nullptr;
-  if (int rc = get_context(&c)) return rc;
-  uint32_t* comp = d_computed;
-  if (!comp) {
-    if (int rc = stream_scratch(c, s, n, &comp)) return rc;
-  }
+  uint32_t* comp = nullptr;
+  const bool args_ok = d_arena && d_offsets && d_lens && d_expected && d_mismatch;
+  if (const int rc = verify_begin(type, args_ok, d_mismatch_count, d_computed, n, s, &c, &comp); rc || !comp) return rc;
   if (type == kTypeNone) {
     HIP_OR_FAIL(launch_zero_words(comp, n, s));
   } else {
@@ -1131,7 +783,7 @@ int hf3fs_crc_verify_blocks(uint8_t type, const void* d_arena, const uint64_t* d
     if (int rc = plan_balance(c, p, src, n, max_len, s)) return rc;
     HIP_OR_FAIL(launch_ranges_arena(type, src, p, comp, c->tables, s));
   }
-  return verify_tail(c, comp, d_expected, d_mismatch, d_mismatch_count, n, s);
+  return verify_tail(comp, d_expected, d_mismatch, d_mismatch_count, n, s);
 }
 
 int hf3fs_crc_combine_batch(uint8_t type, uint32_t* d_acc, const uint32_t* d_crc2, const uint64_t* d_len2,
@@ -1212,6 +864,23 @@ int plan_apply(Context* c, hipStream_t s, uint64_t n, uint32_t max_len, ApplyPla
   return HF3FS_CRC_OK;
 }
 
+// The side stream of a one-shot update call from its fork on.  Whichever way the call
+// leaves, side.join is recorded on the side stream (once) and s waits for it: a side stream
+// left forked would fail the end of a capture and stay in the invalidated capture.
+struct SideJoin {
+  Side side;
+  hipStream_t s = nullptr;
+  bool forked = false, recorded = false;
+  hipError_t record() { return recorded = true, hipEventRecord(side.join, side.side); }
+  hipError_t wait() {
+    forked = false;
+    const hipError_t e = recorded ? hipSuccess : record();
+    const hipError_t w = hipStreamWaitEvent(s, side.join, 0);
+    return e != hipSuccess ? e : w;
+  }
+  ~SideJoin() { if (forked) (void)wait(); }
+};
+
 int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
                            void* stream) {
   if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
@@ -1233,7 +902,6 @@ int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n,
   const uint32_t rep = std::max<uint32_t>(1, options().prehash_rep.load());
   const uint32_t nw = (uint32_t)c->cus * kWaves * rep;
   ApplyPlan ap;
-  Context::Side side;
   if (unfused)
     if (int rc = plan_apply(c, s, n, max_len, &ap)) return rc;
   void* base = nullptr;
@@ -1251,30 +919,29 @@ int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n,
   const ByteRuns runs{sc.run_partial, sc.run_bal, sc.run_boff, sc.run_blocks, prep_runs, rep};
   // ONE zeroing launch: the job maxima, the task count and every ticket counter of this
   // call live in sc.ctl; prep zeroes the per-IO hash outputs itself.
-  hipError_t e = launch_zero_words(sc.ctl, kCtlWords, s);
-  if (e != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "zero: %s", hipGetErrorString(e));
+  HIP_OR_FAIL(launch_zero_words(sc.ctl, kCtlWords, s));
+  SideJoin join;
   if (!unfused) {  // one kernel: prep + payload verify + write (+ delta old-byte hash)
-    e = launch_update_fused(d_ios, n, max_len, type, mode, sc, c->tables,
-                            (uint32_t)std::min<uint64_t>(n, (uint64_t)c->cus), (int)options().apply_nt.load(), s);
-    if (e != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "update fused: %s", hipGetErrorString(e));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n, (uint64_t)c->cus);
+    const int nt = (int)options().apply_nt.load();
+    HIP_OR_FAIL(launch_update_fused(d_ios, n, max_len, type, mode, sc, c->tables, grid, nt, s));
   } else {  // three passes: prep, the pre jobs through k_crc_ranges, apply (+ finalize of most IOs)
-    e = launch_update_prep(d_ios, n, max_len, type, mode, sc, prep_runs, s);
-    if (e != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "update prep: %s", hipGetErrorString(e));
+    HIP_OR_FAIL(launch_update_prep(d_ios, n, max_len, type, mode, sc, prep_runs, s));
     ListSource pre{sc.pre_addr, sc.pre_len, sc.pre_start, 2 * n, 0u};
     if (int rc = run_ranges_list(c, ktype, pre, max_len, sc.pre_out, s, kPreSeg, sc.ctl + kCtlPreMax, nullptr,
                                  sc.ctl + kCtlQueuePre, &runs))
       return rc;
     if (ap.one_shot) {  // every verdict and every IO without a post job, beside the apply
-      if (int rc = c->side_of(s, &side)) return rc;
-      HIP_OR_FAIL(hipEventRecord(side.fork, s));
-      HIP_OR_FAIL(hipStreamWaitEvent(side.side, side.fork, 0));
-      e = launch_update_finalize(d_ios, n, type, mode, sc, c->tables, max_len, 1, false, side.side);
-      if (e != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "update finalize: %s", hipGetErrorString(e));
-      HIP_OR_FAIL(hipEventRecord(side.join, side.side));
+      if (int rc = c->side_of(s, &join.side)) return rc;
+      join.s = s;
+      HIP_OR_FAIL(hipEventRecord(join.side.fork, s));
+      join.forked = true;  // from here on every return joins the side stream again
+      HIP_OR_FAIL(hipStreamWaitEvent(join.side.side, join.side.fork, 0));
+      HIP_OR_FAIL(launch_update_finalize(d_ios, n, type, mode, sc, c->tables, max_len, 1, false, join.side.side));
+      HIP_OR_FAIL(join.record());
     }
-    e = launch_update_apply(d_ios, n, max_len, type, mode, sc, c->tables, true, ap.grid,
-                            (int)options().apply_nt.load(), ap.ptab_cap, ap.hint, s);
-    if (e != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "update apply: %s", hipGetErrorString(e));
+    HIP_OR_FAIL(launch_update_apply(d_ios, n, max_len, type, mode, sc, c->tables, true, ap.grid,
+                                    (int)options().apply_nt.load(), ap.ptab_cap, ap.hint, s));
   }
   ListSource post{sc.post_addr, sc.post_len, sc.post_start, 2 * n, 0u};
   if (int rc = run_ranges_list(c, ktype, post, max_len, sc.post_out, s, 256 << 10, sc.ctl + kCtlPostMax, nullptr,
@@ -1283,10 +950,9 @@ int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n,
   // the last launch also re-checks every payload it reports as mismatched (option audit)
   // the three-pass pipeline's verdicts came from the apply (ticketed) or the side stream
   // (one-shot): only the post-job IOs and the audit are left
-  if (ap.one_shot) HIP_OR_FAIL(hipStreamWaitEvent(s, side.join, 0));
-  e = launch_update_finalize(d_ios, n, type, mode, sc, c->tables, max_len, unfused ? 2 : 0,
-                             options().audit.load() != 0, s);
-  if (e != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "update finalize: %s", hipGetErrorString(e));
+  if (ap.one_shot) HIP_OR_FAIL(join.wait());
+  HIP_OR_FAIL(launch_update_finalize(d_ios, n, type, mode, sc, c->tables, max_len, unfused ? 2 : 0,
+                                     options().audit.load() != 0, s));
   if (options().debug.load()) {  // diagnostics: job maxima and the first pre/post hashes
     uint32_t mx[2] = {0, 0}, pre[4] = {0, 0, 0, 0}, post[4] = {0, 0, 0, 0};
     uint64_t plen[4] = {0, 0, 0, 0};
@@ -1436,12 +1102,6 @@ int hf3fs_crc_file_digest_batch(const hf3fs_crc_block_digest* d_blocks, const ui
 // streams while the next stage is packed; the pieces of each buffer are then
 // stitched on the host with the combine algebra:
 //   raw(buf, start) = start * x^(8 len) ^ sum_j lin(piece_j) * x^(8 * bytes after piece j).
-}  // extern "C"
-namespace {
-int create_host_staged(Context* c, uint8_t type, const void* const* h_bufs, const uint64_t* h_lens,
-                       const uint32_t* h_starts, uint32_t* h_out, uint64_t n);
-}
-extern "C" {
 int hf3fs_crc_create_host(uint8_t type, const void* const* h_bufs, const uint64_t* h_lens, const uint32_t* h_starts,
                           uint32_t* h_out, uint64_t n) {
   if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);

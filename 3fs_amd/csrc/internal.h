@@ -10,6 +10,9 @@ struct DeviceTables;
 int set_error(int code, const char* msg);
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// Fills the host copy of a device context's constant tables (device_tables.cc).
+void build_device_tables(DeviceTables& T);
+
 // Constant tables of the calling thread's current device (context created on first use).
 int current_tables(const DeviceTables** out);
 

@@ -1097,6 +1097,98 @@ def test_update_one_shot_hint_across_release_stream(hf, orc, dev, rep, opts):
     assert L.anomalies(0)["count"] == 0
 
 
+def test_pair_state_every_member_across_release_stream(hf, orc, dev, opts):
+    """Everything the library keeps per (stream, thread) pair, on two streams A and B of one
+    thread, across release_stream: the verify buffer (verify_batch, d_computed = NULL), the
+    call buffer, hint word and side stream (two consecutive three-pass DELTA updates: the
+    second takes the one-shot apply), the ticket counter (a ragged create_batch of 5,000
+    ranges) and the balance region (70,000 whole-range tasks, most of them empty, the longest
+    past the prefetch bound: more than 16 per resident wave).  The set runs on A and on B,
+    A is released, then the set again on B (its state must be untouched) and on A (every
+    member created anew, its first update a first call again: the ticketed apply); every
+    result vs the oracle or ChunkReplica::update restated."""
+    _set_pipeline(opts, "unfused")
+    L = hf._lib
+    L.anomalies(0, reset=True)
+    A, B = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    rng = np.random.default_rng(4100)
+    size = 16 << 20
+    host = rng.integers(0, 256, size, dtype=np.uint8)
+    arena = to_dev(host, dev)
+
+    def ranges(n, lens):
+        offs = rng.integers(0, size - 40001, n)
+        ref = np.array([orc.crc32c_raw(host[o:o + l]) for o, l in zip(offs, lens)], dtype=np.uint32)
+        return (n, addr_tensor([arena.data_ptr() + int(o) for o in offs], dev), torch.tensor(lens, device=dev),
+                int(lens.max()), ref)
+
+    ragged = ranges(5000, rng.integers(1, 40001, 5000))
+    lens = np.zeros(70_000, dtype=np.int64)
+    live = rng.random(lens.size) < 0.05
+    lens[live] = rng.integers(1, 40001, int(live.sum()))
+    lens[30000:30040] = 40000
+    lens[:50] = 0
+    lens[-50:] = 0
+    skewed = ranges(lens.size, lens)
+    bad = np.sort(rng.choice(ragged[0], 9, replace=False))
+    exp = ragged[4].copy()
+    exp[bad] ^= 0x40
+    d_exp = torch.tensor(exp.view(np.int32), device=dev)
+
+    n, cs = 64, 128 * 1024
+    chunks = [bytearray(cs) for _ in range(n)]
+    sizes, cks = [0] * n, [(1, 0)] * n
+    dchunks = torch.zeros(n * cs, dtype=torch.uint8, device=dev)
+    payload = torch.zeros(n * cs, dtype=torch.uint8, device=dev)
+
+    def touch_every_member(st, tag):
+        for rnd in range(2):  # the pair's first update: ticketed apply; the second: one-shot
+            ios = _random_ios(rng, n, cs, sizes, cks, ["rand", "mixed"][rnd])
+            arr = (hf.UpdateIO * n)()
+            host_payload = np.zeros(n * cs, dtype=np.uint8)
+            expect = _update_round(hf, orc, rng, ios, arr, dchunks, chunks, sizes, cks, cs, payload.data_ptr(),
+                                   host_payload)
+            payload.copy_(to_dev(host_payload, dev))
+            d_ios = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(dev)
+            torch.cuda.synchronize()
+            L.update_batch(1, d_ios, n, cs, mode=1, stream=st)
+            st.synchronize()
+            res = (hf.UpdateIO * n).from_buffer_copy(d_ios.cpu().numpy().tobytes())
+            h = dchunks.cpu().numpy()
+            for c in range(n):
+                rc, sz, ck, kase = expect[c]
+                assert res[c].status == rc, (tag, rnd, c, ios[c])
+                assert res[c].checksum_case == kase, (tag, rnd, c, ios[c])
+                assert res[c].out_size == sz, (tag, rnd, c, ios[c])
+                assert (res[c].out_checksum_type, res[c].out_checksum) == tuple(ck), (tag, rnd, c, ios[c])
+                sizes[c], cks[c] = sz, tuple(ck)
+                assert bytes(h[c * cs:c * cs + sz]) == bytes(chunks[c][:sz]), (tag, rnd, c)
+        m, addrs, ln, mx, ref = ragged
+        mism = torch.zeros(m, dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+        out = torch.zeros(m, dtype=torch.int32, device=dev)
+        k, kaddrs, kln, kmx, kref = skewed
+        kout = torch.zeros(k, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        L.verify_batch(1, addrs, ln, d_exp, mism, cnt, m, mx, stream=st)  # the pair's verify buffer
+        L.create_batch(1, addrs, ln, out, m, mx, stream=st)  # ticket counter
+        L.create_batch(1, kaddrs, kln, kout, k, kmx, stream=st)  # balance region
+        st.synchronize()
+        assert int(cnt.item()) == bad.size, tag
+        assert np.array_equal(np.nonzero(mism.cpu().numpy())[0], bad), tag
+        assert np.array_equal(u32(out), ref), tag
+        assert np.array_equal(u32(kout), kref), tag
+
+    touch_every_member(A, "A")
+    touch_every_member(B, "B")
+    L.release_stream(A)
+    touch_every_member(B, "B after release(A)")
+    touch_every_member(A, "A after release(A)")
+    L.release_stream(A)
+    L.release_stream(B)
+    assert L.anomalies(0)["count"] == 0
+
+
 @pytest.mark.parametrize("captured", [False, True], ids=["pair_buffer", "captured"])
 def test_update_incident_io_poisoned(hf, orc, dev, captured, opts):
     """The incident's exact IO (scripts/probe_first_call.cpp, tests/cpp/test_checksuminfo.cpp's first

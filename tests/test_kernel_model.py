@@ -126,7 +126,7 @@ def test_model_segmented_matches_oracle(orc, align, length, seg):
 
 
 def _short_tables(orc, poly):
-    """PolyTables::dw (x^32 dword slices), ::b8 (x^8 byte table) as built in hf3fs_crc_api.hip."""
+    """PolyTables::dw (x^32 dword slices), ::b8 (x^8 byte table) as built in device_tables.cc."""
     x32, x8 = xpow_bits(orc, 32, poly), xpow_bits(orc, 8, poly)
     dw = [[gf(orc, b << (8 * k), x32, poly) for b in range(256)] for k in range(4)]
     b8 = [gf(orc, b, x8, poly) for b in range(256)]
