@@ -293,9 +293,10 @@ int pair_counter(Context* c, hipStream_t s, uint32_t** out) {
 // capture it is memory of the captured call alone, owned by the captured graph and freed
 // after the graph is gone (capture_malloc): the graph may be replayed on any stream, and a
 // replay never touches pair memory that release_stream or a later growth freed.
-// Option poison (test only): the words of a verify or call buffer are first filled with that
-// pattern on the stream, so a call that read a word before writing it would see junk
-// (tests/test_gpu_parity.py::test_update_batch_poisoned_scratch).
+// Option poison (test only): the words of a verify, call or balance buffer are first filled with
+// that pattern on the stream, so a call that read a word before writing it (a bal[] boundary
+// k_bal_assign never placed) would see junk (tests/test_gpu_parity.py::
+// test_update_batch_poisoned_scratch, tests/test_gpu_batch_contexts.py).
 enum class Mem { kVerify, kCall, kBalance, kCounter };
 int call_memory(Context* c, hipStream_t s, Mem what, size_t words, uint32_t** out) {
   bool capturing = false;
@@ -309,7 +310,7 @@ int call_memory(Context* c, hipStream_t s, Mem what, size_t words, uint32_t** ou
                                          : pair_buffer(c, buffer[(int)what], s, words, what == Mem::kCall, out);
     if (rc) return rc;
   }
-  if (what == Mem::kVerify || what == Mem::kCall)
+  if (what == Mem::kVerify || what == Mem::kCall || what == Mem::kBalance)
     if (const uint32_t pattern = options().poison.load()) HIP_OR_FAIL(launch_fill_words(*out, words, pattern, s));
   return HF3FS_CRC_OK;
 }
@@ -401,6 +402,10 @@ int plan_balance(Context* c, Plan& p, const Src& src, uint64_t n, uint64_t max_l
   uint32_t* bal = sc + 2 * Context::kBalBlocksMax;
   HIP_OR_FAIL(launch_balance(src, n, (uint32_t)nw, partial, nblocks, bal, s));
   p.bal = bal;
+  // The kernel drops its ticket queue here (n > 16 nw), so the plan carries none: launch_poly takes
+  // the range-stream kernel (option range_stream) only for a plan without a queue, and with the
+  // counter launch_prepare handed over the option never reached it.
+  p.queue = nullptr;
   return HF3FS_CRC_OK;
 }
 

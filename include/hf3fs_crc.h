@@ -90,9 +90,10 @@ int hf3fs_crc_graph_scratch_stats(uint64_t *live_buffers, uint64_t *live_bytes, 
  * (4|8|16), frame_stream (auto|0|1), frame_segw, debug, audit, range_stream, list_runs,
  * prehash_rep (1..8 byte runs per wave for the update pre hash and list_runs batches).
  * Test only, settable through set_option alone (the environment is ignored for them):
- * poison (every library scratch word handed to a call is first set to this value,
- * 0 = off) and fault_io (IO fault_io - 1 of every update batch is hashed from a wrong
- * start value, 0 = off: the self-check's end-to-end test). */
+ * poison (every library scratch word handed to a call -- verify values, call scratch and
+ * the byte-balance region -- is first set to this value, 0 = off) and fault_io (IO
+ * fault_io - 1 of every update batch is hashed from a wrong start value, 0 = off: the
+ * self-check's end-to-end test). */
 int hf3fs_crc_set_option(const char *name, const char *value);
 int hf3fs_crc_get_option(const char *name, char *out, size_t cap);
 
