@@ -20,6 +20,7 @@ MODE_REFERENCE, MODE_DELTA = 0, 1
 OK, INVALID_ARG, CHUNK_READ_FAILED, CHECKSUM_MISMATCH, CLIENT_CHECKSUM_MISMATCH, DEVICE_ERROR = (
     0, 3, 4010, 4080, 7015, 9001)
 SERDE_INSUFFICIENT_LENGTH = 40
+NOT_APPLIED = 9002  # update_ordered: the IO was not reached (max_rounds); chunk untouched, resubmit it
 
 
 class Hf3fsCrcError(RuntimeError):
@@ -217,6 +218,9 @@ SIGNATURES = {
     "hf3fs_crc_combine_batch": (_int, [_u8, _vp, _vp, _vp, _u64, _vp]),
     "hf3fs_crc_update_batch": (_int, [_u8, _vp, _u64, _u32, _int, _vp]),
     "hf3fs_crc_update_scratch_bytes": (ctypes.c_size_t, [_u64, _int]),
+    "hf3fs_crc_update_ordered": (_int, [_u8, _vp, _u64, _u32, _int, _u32, _vp, _vp]),
+    "hf3fs_crc_update_ordered_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int, _u32]),
+    "hf3fs_crc_pair_scratch_stats": (_int, [_vp, _vp, _vp]),
     "hf3fs_crc_read_result_batch": (_int, [_u8, _vp, _u64, _u32, _vp]),
     "hf3fs_crc_file_digest_batch": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "hf3fs_crc_file_digest_batch_ex": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
@@ -340,6 +344,25 @@ def update_scratch_bytes(n, mode=MODE_REFERENCE):
     """Bytes of library-owned scratch one update_batch of n IOs takes (the calling
     (stream, thread) pair's buffer, or a captured call's own; never the stream-ordered pool)."""
     return int(load().hf3fs_crc_update_scratch_bytes(n, mode))
+
+
+def update_ordered(ctype, ios, n, max_len, max_rounds, mode=MODE_REFERENCE, info=None, stream=None):
+    """hf3fs_crc_update_ordered: n IOs in arrival order, chunks may repeat (at most max_rounds IOs
+    per chunk are applied, the rest come back NOT_APPLIED); info: two device u32 words or None."""
+    return check(load().hf3fs_crc_update_ordered(ctype, _p(ios), n, max_len, mode, max_rounds, _p(info), _s(stream)))
+
+
+def update_ordered_scratch_bytes(n, max_len, max_rounds, mode=MODE_REFERENCE):
+    """Bytes of library-owned scratch one update_ordered of this shape takes (0: rejected arguments)."""
+    return int(load().hf3fs_crc_update_ordered_scratch_bytes(n, max_len, mode, max_rounds))
+
+
+def pair_scratch_stats(stream=None):
+    """{call_bytes, allocations}: the calling (stream, thread) pair's call scratch and the
+    process's count of pair-buffer allocations and growths (test aid)."""
+    v = (ctypes.c_uint64 * 2)()
+    check(load().hf3fs_crc_pair_scratch_stats(_s(stream), ctypes.addressof(v), ctypes.addressof(v) + 8))
+    return {"call_bytes": int(v[0]), "allocations": int(v[1])}
 
 
 def set_option(name, value):

@@ -356,7 +356,16 @@ __device__ __forceinline__ void byte_run(const Src& src, uint32_t w, const uint3
     const uint64_t eo = i == iend ? eo_last : len;
     if (i == iend && eo == 0) break;  // the next run's range
     if (len == 0) {  // create(type, buf, 0, start) == {type, start}
-      if (lane == 0) atomicXor(out + i, src.start_of(i));
+      // A stretch of empty ranges (the no-op records of an update_ordered round are thousands in a
+      // row), 64 at a time: lane l looks at range i + l, the lanes before the first non-empty one
+      // add their start terms.  Ranges below iend are this run's; iend itself is never empty here.
+      const uint32_t lim = iend < n ? iend : n;
+      const uint32_t j = i + (uint32_t)lane;
+      const bool empty = lane == 0 || (j < lim && src.length(j) == 0);  // (lane 0: range i, as before)
+      const uint64_t stop = ~__ballot(empty);
+      const uint32_t cnt = stop ? (uint32_t)(__ffsll((unsigned long long)stop) - 1) : 64u;
+      if ((uint32_t)lane < cnt) atomicXor(out + j, src.start_of(j));
+      i += cnt - 1;
       continue;
     }
     if (so < eo) hash_part<POLY, NT>(src, i, len, so, eo, out, T, lj, lc, lane);

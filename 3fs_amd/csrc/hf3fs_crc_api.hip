@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -26,6 +27,7 @@
 #include "digest_kernels.h"
 #include "internal.h"
 #include "options.h"
+#include "order_kernels.h"
 #include "update_kernels.h"
 
 static_assert(sizeof(hf3fs_crc_update_io) == 56, "hf3fs_crc_update_io ABI layout");
@@ -75,7 +77,8 @@ struct PairState {
   Scratch call;                 // scratch of update / record / frame / digest batches
   Scratch balance;              // byte-balance region of whole-range launches (bal_words words)
   uint32_t* counter = nullptr;  // ticket counter: a 16 B slot of a shared slab, not owned
-  uint32_t hint = kNoHint;      // slot of the one-shot apply's pinned hint word
+  uint32_t hint[2] = {kNoHint, kNoHint};  // slots of the one-shot apply's pinned hint words:
+                                          // [0] update_batch, [1] round 0 of update_ordered
   Side side;
 };
 
@@ -124,7 +127,7 @@ struct Context {
   uint32_t hint_uses[kHintSlots] = {};
   std::vector<uint32_t> hint_free;
   uint32_t hint_next = 0;
-  int hint_word(hipStream_t s, uint64_t** host, uint64_t** dev) {
+  int hint_word(hipStream_t s, int which, uint64_t** host, uint64_t** dev) {
     std::lock_guard<std::mutex> lk(mu);
     if (!hint_host) {  // (the pair's first update call may be a captured one)
       RelaxedCapture relaxed;
@@ -133,7 +136,7 @@ struct Context {
       memset(hint_host, 0, kHintSlots * 8);
       HIP_OR_FAIL(hipHostGetDevicePointer((void**)&hint_dev, hint_host, 0));
     }
-    uint32_t& slot = pairs[stream_key(s)].hint;
+    uint32_t& slot = pairs[stream_key(s)].hint[which];
     if (slot == kNoHint) {
       if (!hint_free.empty()) {
         slot = hint_free.back();
@@ -233,6 +236,8 @@ int is_capturing(hipStream_t s, bool* capturing) {
   return HF3FS_CRC_OK;
 }
 
+std::atomic<uint64_t> g_pair_allocs{0};  // allocations and growths of pair buffers (hf3fs_crc_pair_scratch_stats)
+
 // The calling (stream, thread) pair's buffer `member`, at least `words` long (roomy: sized
 // up to a multiple of 64 Ki words and at least doubled, else exactly `words`).  Only that
 // pair ever uses the buffer and only this thread launched work on it, all of it on s, so
@@ -250,6 +255,7 @@ int pair_buffer(Context* c, Scratch PairState::*member, hipStream_t s, size_t wo
     if (slot.words < words) slot = Scratch{};
   }
   if (e.words < words) {
+    g_pair_allocs.fetch_add(1, std::memory_order_relaxed);
     const size_t grow_to = roomy ? std::max<size_t>((words + 65535) / 65536 * 65536, 2 * e.words) : words;
     hipError_t err = e.ptr ? hipStreamSynchronize(s) : hipSuccess;
     if (err == hipSuccess && e.ptr) {
@@ -576,10 +582,11 @@ int hf3fs_crc_release_stream(void* stream) {
       }
       // the pair's one-shot hint word: cleared (the slot's next call starts with the ticketed
       // apply that counts its pieces), the slot back on the free list with its last pair
-      if (const uint32_t slot = it->second.hint; slot != kNoHint) {
-        __atomic_store_n(c->hint_host + slot, 0ull, __ATOMIC_RELEASE);
-        if (--c->hint_uses[slot] == 0) c->hint_free.push_back(slot);
-      }
+      for (const uint32_t slot : it->second.hint)
+        if (slot != kNoHint) {
+          __atomic_store_n(c->hint_host + slot, 0ull, __ATOMIC_RELEASE);
+          if (--c->hint_uses[slot] == 0) c->hint_free.push_back(slot);
+        }
       gone.push_back(it->second);
       it = c->pairs.erase(it);
     }
@@ -844,16 +851,26 @@ struct ApplyPlan {
   uint64_t ptab_cap = 0;
   uint64_t* hint = nullptr;  // device view of the pair's pinned hint word
 };
-int plan_apply(Context* c, hipStream_t s, uint64_t n, uint32_t max_len, ApplyPlan* ap) {
+uint32_t apply_piece_shift() {
+  const uint32_t kib = options().apply_piece_kib.load();
+  return kib <= 4 ? 12 : kib <= 8 ? 13 : 14;
+}
+// Piece-table entries a one-shot apply of this shape would take, 0 where the options or the size
+// rule it out (then every call of the shape is ticketed).
+uint64_t one_shot_cap(uint64_t n, uint32_t max_len) {
+  const uint64_t cap = update_piece_cap(n, max_len, apply_piece_shift());
+  return options().apply_grid.load() == 0 || cap >= (1ull << 31) || cap * 4 > (1ull << 30) ? 0 : cap;
+}
+// which: the pair's hint word -- 0 update_batch's, 1 the one of update_ordered's first round.
+int plan_apply(Context* c, hipStream_t s, uint64_t n, uint32_t max_len, ApplyPlan* ap, int which = 0) {
   const Options& o = options();
-  const uint32_t kib = o.apply_piece_kib.load();
-  ap->shift = kib <= 4 ? 12 : kib <= 8 ? 13 : 14;
+  ap->shift = apply_piece_shift();
   ap->grid = (uint32_t)c->cus * 8;
   uint64_t* host = nullptr;
-  if (int rc = c->hint_word(s, &host, &ap->hint)) return rc;
+  if (int rc = c->hint_word(s, which, &host, &ap->hint)) return rc;
   const int mode = o.apply_grid.load();
-  const uint64_t cap = update_piece_cap(n, max_len, ap->shift);
-  if (mode == 0 || cap >= (1ull << 31) || cap * 4 > (1ull << 30)) return HF3FS_CRC_OK;  // tickets
+  const uint64_t cap = one_shot_cap(n, max_len);
+  if (!cap) return HF3FS_CRC_OK;  // tickets
   const uint64_t h = __atomic_load_n(host, __ATOMIC_ACQUIRE);
   const uint64_t prev_pieces = h >> 32, prev_n = h & 0xffffffffull;
   if (mode == 2) {  // test: a small grid, every workgroup loops over several pieces
@@ -886,6 +903,20 @@ struct SideJoin {
   ~SideJoin() { if (forked) (void)wait(); }
 };
 
+// What the options make of an update call in `mode`: the pipeline, its apply pieces and the
+// waves of its hash launches (pre-hash byte runs: prehash_rep runs per wave, Plan::run_rep).
+struct UpdateGeom {
+  bool unfused = false;
+  uint32_t pieces = 0, piece_min = 0, rep = 1, nw = 0;
+};
+static void update_geometry(const Context* c, int mode, UpdateGeom* g) {
+  update_pipeline(mode, &g->unfused, &g->pieces, &g->piece_min);
+  g->rep = std::max<uint32_t>(1, options().prehash_rep.load());
+  g->nw = (uint32_t)c->cus * kWaves * g->rep;
+}
+static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
+                      const UpdateGeom& g, const ApplyPlan& ap, void* base, hipStream_t s);
+
 int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
                            void* stream) {
   if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
@@ -896,21 +927,27 @@ int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n,
   Context* c = nullptr;
   if (int rc = get_context(&c)) return rc;
   hipStream_t s = (hipStream_t)stream;
+  UpdateGeom g;
+  update_geometry(c, mode, &g);
+  ApplyPlan ap;
+  if (g.unfused)
+    if (int rc = plan_apply(c, s, n, max_len, &ap)) return rc;
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, update_scratch_bytes(n, g.pieces, g.nw, ap.ptab_cap), &base)) return rc;
+  return update_run(c, type, d_ios, n, max_len, mode, g, ap, base, s);
+}
+
+// One pass of the update pipeline over n IOs on DISTINCT chunks, on scratch the caller got for it
+// (update_scratch_bytes(n, g.pieces, g.nw, ap.ptab_cap) at base): hf3fs_crc_update_batch, and every
+// round of hf3fs_crc_update_ordered.
+static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
+                      const UpdateGeom& g, const ApplyPlan& ap, void* base, hipStream_t s) {
   const uint8_t ktype = type == kTypeNone ? kTypeCrc32c : type;
-  bool unfused = false;
-  uint32_t pieces = 0, piece_min = 0;
-  update_pipeline(mode, &unfused, &pieces, &piece_min);
+  const bool unfused = g.unfused;
+  const uint32_t pieces = g.pieces, piece_min = g.piece_min, rep = g.rep, nw = g.nw;
   // Pre-hash task size: 512 KiB segments of the payload / old-byte jobs (A/B on d3 DELTA:
   // 1.766-1.772 ms per batch vs 1.788-1.797 at 256 KiB, 1.85 at 1 MiB; gpurun_out r03 seg sweep).
   constexpr uint64_t kPreSeg = 512 << 10;
-  // pre-hash byte runs: prehash_rep runs per wave (option; Plan::run_rep)
-  const uint32_t rep = std::max<uint32_t>(1, options().prehash_rep.load());
-  const uint32_t nw = (uint32_t)c->cus * kWaves * rep;
-  ApplyPlan ap;
-  if (unfused)
-    if (int rc = plan_apply(c, s, n, max_len, &ap)) return rc;
-  void* base = nullptr;
-  if (int rc = call_scratch(c, s, update_scratch_bytes(n, pieces, nw, ap.ptab_cap), &base)) return rc;
   UpdateScratch sc;
   update_scratch_carve(base, n, pieces, piece_min, nw, ap.ptab_cap, &sc);
   sc.piece_shift = ap.shift;
@@ -971,6 +1008,83 @@ int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n,
             (unsigned long long)n, mode, mx[0], mx[1], pre[0], pre[1], (unsigned long long)plen[0],
             (unsigned long long)plen[1], post[0], post[1]);
   }
+  return HF3FS_CRC_OK;
+}
+
+// The one scratch request of an ordered call: the pipeline's part first -- with the piece table
+// of a one-shot apply whenever the options allow one, whether or not this call's first round
+// takes it (the pair's hint decides that from call to call, and no later call may need more than
+// the first of a shape got) -- and the planner's arrays behind it.
+static size_t ordered_pipeline_bytes(const UpdateGeom& g, uint64_t n, uint32_t max_len) {
+  const size_t b = update_scratch_bytes(n, g.pieces, g.nw, g.unfused ? one_shot_cap(n, max_len) : 0);
+  return (b + 63) & ~size_t(63);
+}
+static int ordered_args(uint8_t type, int mode, uint32_t max_rounds) {
+  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
+  if (mode != HF3FS_UPDATE_MODE_REFERENCE && mode != HF3FS_UPDATE_MODE_DELTA)
+    return fail(HF3FS_CRC_INVALID_ARG, "unknown update mode %d", mode);
+  if (max_rounds < 1 || max_rounds > 64)
+    return fail(HF3FS_CRC_INVALID_ARG, "max_rounds %u is not in 1..64", max_rounds);
+  return HF3FS_CRC_OK;
+}
+constexpr uint64_t kOrderedMaxIos = 1ull << 30;  // 32-bit IO indices, a table of 2 n slots
+
+size_t hf3fs_crc_update_ordered_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds) {
+  if (ordered_args(kTypeCrc32c, mode, max_rounds) || n == 0 || n > kOrderedMaxIos) return 0;
+  Context* c = nullptr;
+  if (get_context(&c)) return 0;
+  UpdateGeom g;
+  update_geometry(c, mode, &g);
+  return ordered_pipeline_bytes(g, n, max_len) + order_scratch_bytes(n);
+}
+
+int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
+                             uint32_t max_rounds, uint32_t* d_info, void* stream) {
+  if (int rc = ordered_args(type, mode, max_rounds)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    if (d_info) HIP_OR_FAIL(launch_zero_words(d_info, 2, s));
+    return HF3FS_CRC_OK;
+  }
+  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  UpdateGeom g;
+  update_geometry(c, mode, &g);
+  // Round 0 is planned like an update_batch of the n records (with every chunk distinct it IS that
+  // call), on a hint word of its own: what an ordered call counts never sizes the grid of a plain
+  // update_batch on the same pair.  Later rounds shrink fast and are padded to n records, so a
+  // pieces-per-IO figure says nothing about them: they take the ticketed apply, which needs none.
+  ApplyPlan first, later;
+  if (g.unfused) {
+    if (int rc = plan_apply(c, s, n, max_len, &first, 1)) return rc;
+    later.shift = first.shift;
+    later.grid = (uint32_t)c->cus * 8;
+  }
+  const size_t pipe_bytes = ordered_pipeline_bytes(g, n, max_len);
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, pipe_bytes + order_scratch_bytes(n), &base)) return rc;
+  OrderScratch os;
+  order_scratch_carve((uint8_t*)base + pipe_bytes, n, &os);
+  HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
+  for (uint32_t r = 0; r < max_rounds; ++r) {
+    HIP_OR_FAIL(launch_order_step(d_ios, n, r, max_rounds, os, nullptr, s));
+    if (int rc = update_run(c, type, os.round, n, max_len, mode, g, r ? later : first, base, s)) return rc;
+  }
+  HIP_OR_FAIL(launch_order_step(d_ios, n, max_rounds, max_rounds, os, d_info, s));
+  return HF3FS_CRC_OK;
+}
+
+int hf3fs_crc_pair_scratch_stats(void* stream, uint64_t* call_bytes, uint64_t* allocations) {
+  if (call_bytes) {
+    Context* c = nullptr;
+    if (int rc = get_context(&c)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const auto it = c->pairs.find(stream_key((hipStream_t)stream));
+    *call_bytes = it == c->pairs.end() ? 0 : (uint64_t)it->second.call.words * 4;
+  }
+  if (allocations) *allocations = g_pair_allocs.load(std::memory_order_relaxed);
   return HF3FS_CRC_OK;
 }
 

@@ -44,8 +44,10 @@ enum {
   HF3FS_CRC_CHECKSUM_MISMATCH = 4080,         /* StorageCode::kChecksumMismatch (:186) */
   HF3FS_CRC_CHUNK_NOT_FOUND = 7007,           /* StorageClientCode::kChunkNotFound (:228) */
   HF3FS_CRC_CLIENT_CHECKSUM_MISMATCH = 7015,  /* StorageClientCode::kChecksumMismatch (:236) */
-  HF3FS_CRC_DEVICE_ERROR = 9001               /* HIP runtime failure, or an update IO whose verify the
+  HF3FS_CRC_DEVICE_ERROR = 9001,              /* HIP runtime failure, or an update IO whose verify the
                                                  self-check contradicted (no reference equivalent) */
+  HF3FS_CRC_NOT_APPLIED = 9002                /* no reference equivalent: the IO was not reached (see max_rounds);
+                                                 chunk untouched, resubmit it */
 };
 
 /* ------------------------------------------------------------------------ */
@@ -301,6 +303,52 @@ int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io *d_ios, uint64_t n,
  * The figure is for the ticketed apply; a call with the one-shot apply adds a piece
  * table of 4 B per 8 KiB piece, n * (max_len / 8 KiB + 4) entries. */
 size_t hf3fs_crc_update_scratch_bytes(uint64_t n, int mode);
+
+/* A queue of n IOs in ARRIVAL ORDER whose IOs may share a chunk: equivalent to applying d_ios[0],
+ * d_ios[1], ... d_ios[n-1] one at a time, each as a one-IO hf3fs_crc_update_batch with the same
+ * type, max_len and mode -- the per-chunk serialisation the reference gets from the chunk lock
+ * around ChunkReplica::update (one UpdateWorker job per IO, each starting from the ChunkMetadata the
+ * previous one left).  IOs on different chunks run in parallel.
+ * Identity: two IOs address the same chunk iff their `chunk` fields are equal.  Chunks of different
+ * base addresses whose byte ranges overlap are undefined, as for update_batch; so is a payload
+ * that overlaps any chunk of the batch.  An IO with chunk == 0 is a chunk of its own.
+ * State hand-over: the first IO of a chunk, in index order, takes chunk_size, chunk_checksum_type
+ * and chunk_checksum from its own record.  For every later IO of that chunk these three input
+ * fields are ignored and OVERWRITTEN with the state its predecessor left, so the caller reads what
+ * each IO started from.  Output fields and status keep their meaning for every IO.  An IO that
+ * fails (_CHECKSUM_MISMATCH, _INVALID_ARG, _DEVICE_ERROR) leaves bytes and state untouched and its
+ * successor starts from the state the failed IO started from: the reference's behaviour when an
+ * update fails under the chunk lock.
+ * Depth bound: max_rounds in 1..64 (else kInvalidArg) is the largest number of IOs per chunk one
+ * call applies; the caller states it so that the call needs no host readback.  An IO with
+ * max_rounds or more earlier IOs on its chunk gets status HF3FS_CRC_NOT_APPLIED, checksum_case 0,
+ * and input and output state fields equal to the state after the chunk's last applied IO; its
+ * chunk bytes are not touched by it (resubmit it unchanged, with the other IOs of its chunk in the
+ * same order).  d_info may be NULL; else two device words SET by the call: [0] the longest chain
+ * of the batch (uncapped), [1] the number of NOT_APPLIED IOs.
+ * With all chunks distinct the call writes exactly the bytes hf3fs_crc_update_batch writes, into
+ * the IO records and into the chunks, under every option; the error returns match too (unknown
+ * type or mode, null d_ios with n > 0 -> kInvalidArg, n == 0 -> OK; all checked before any device
+ * is touched).
+ * Stream behaviour: asynchronous on `stream`, no host synchronisation, nothing read back from the
+ * device; capturable, also as the process's first library call.  Ranking happens in kernels: a
+ * replayed graph re-plans from what d_ios holds at replay time.  Scratch follows update_batch's
+ * lifetime rules (per (stream, thread) outside a capture, graph-owned inside one, never the
+ * stream-ordered pool), and every scratch word the call reads it wrote first (option poison).
+ * Cost: a hash table of the chunk addresses, then max_rounds passes of the update pipeline over
+ * n records of which pass r holds the IOs with r earlier IOs on their chunk (the rest are no-op
+ * records), so size max_rounds to the queue, not to 64.  Ranking walks, per IO, the list of its
+ * chunk's IOs: O(multiplicity) per IO -- one chunk taking all n IOs costs n^2 list steps. */
+int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io *d_ios, uint64_t n, uint32_t max_len, int mode,
+                             uint32_t max_rounds, uint32_t *d_info, void *stream);
+/* Bytes of scratch one such call takes, for the pipeline the options select and including the
+ * one-shot apply's piece table for max_len wherever a call of this shape may use it: after one
+ * call of the largest (n, max_len, max_rounds) of a mode, no later call on the pair grows the
+ * buffer.  0 for arguments the call would reject. */
+size_t hf3fs_crc_update_ordered_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds);
+/* Test aid: *call_bytes = bytes of the calling (stream, thread) pair's call scratch (0: none yet),
+ * *allocations = allocations and growths of pair buffers in this process so far; either may be NULL. */
+int hf3fs_crc_pair_scratch_stats(void *stream, uint64_t *call_bytes, uint64_t *allocations);
 
 /* ------------------------------------------------------------------------ */
 /* read results: AioReadJob::setResult checksum part                          */
