@@ -11,7 +11,8 @@ Contents:
   node.py         multi-GPU sharding by chain id + RCCL digest all-gather
 """
 from . import _lib  # noqa: F401
-from ._lib import (CHECKSUM_MISMATCH, CRC32, CRC32C, DEVICE_ERROR, INVALID_ARG, MODE_DELTA, MODE_REFERENCE, NONE,  # noqa: F401
-                   NOT_APPLIED, OK, UPDATE_EXTEND, UPDATE_TRUNCATE, UPDATE_WRITE, Hf3fsCrcError, UpdateIO, load,
-                   update_ordered, update_ordered_scratch_bytes)
+from ._lib import (CHECKSUM_MISMATCH, CRC32, CRC32C, DEVICE_ERROR, FLAG_ENGINE, FLAG_SYNCING,  # noqa: F401
+                   INVALID_ARG, MODE_DELTA, MODE_REFERENCE, NONE, NOT_APPLIED, OK, UPDATE_EXTEND,
+                   UPDATE_TRUNCATE, UPDATE_WRITE, Hf3fsCrcError, UpdateIO, load, update_cow,
+                   update_cow_scratch_bytes, update_ordered, update_ordered_scratch_bytes)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

@@ -54,6 +54,8 @@ class UpdateIO(ctypes.Structure):
 
 assert ctypes.sizeof(UpdateIO) == 56
 UPDATE_FLAG_ENGINE = 1
+UPDATE_FLAG_SYNCING = 2  # a resync write: WRITE at offset 0, out_size = length, no old byte kept
+FLAG_ENGINE, FLAG_SYNCING = UPDATE_FLAG_ENGINE, UPDATE_FLAG_SYNCING
 DIGEST_FILL_ZERO = 1  # hf3fs_crc_file_digest_batch_ex flags
 # UpdateIO.checksum_case (HF3FS_CKCASE_*): the reference's checksum counter for the IO
 CKCASE_NONE, CKCASE_REUSE, CKCASE_COMBINE, CKCASE_RECOMPUTE = 1, 2, 3, 4
@@ -220,6 +222,8 @@ SIGNATURES = {
     "hf3fs_crc_update_scratch_bytes": (ctypes.c_size_t, [_u64, _int]),
     "hf3fs_crc_update_ordered": (_int, [_u8, _vp, _u64, _u32, _int, _u32, _vp, _vp]),
     "hf3fs_crc_update_ordered_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int, _u32]),
+    "hf3fs_crc_update_cow_batch": (_int, [_u8, _vp, _vp, _u64, _u32, _int, _vp]),
+    "hf3fs_crc_update_cow_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int]),
     "hf3fs_crc_pair_scratch_stats": (_int, [_vp, _vp, _vp]),
     "hf3fs_crc_read_result_batch": (_int, [_u8, _vp, _u64, _u32, _vp]),
     "hf3fs_crc_file_digest_batch": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
@@ -355,6 +359,17 @@ def update_ordered(ctype, ios, n, max_len, max_rounds, mode=MODE_REFERENCE, info
 def update_ordered_scratch_bytes(n, max_len, max_rounds, mode=MODE_REFERENCE):
     """Bytes of library-owned scratch one update_ordered of this shape takes (0: rejected arguments)."""
     return int(load().hf3fs_crc_update_ordered_scratch_bytes(n, max_len, mode, max_rounds))
+
+
+def update_cow(ctype, ios, dst, n, max_len, mode=MODE_REFERENCE, stream=None):
+    """hf3fs_crc_update_cow_batch: update_batch with a device array of n destination addresses
+    (None: every IO in place; entry 0 or the IO's chunk: that IO in place)."""
+    return check(load().hf3fs_crc_update_cow_batch(ctype, _p(ios), _p(dst), n, max_len, mode, _s(stream)))
+
+
+def update_cow_scratch_bytes(n, max_len, mode=MODE_REFERENCE):
+    """Bytes of library-owned scratch one update_cow_batch of this shape takes (0: rejected arguments)."""
+    return int(load().hf3fs_crc_update_cow_scratch_bytes(n, max_len, mode))
 
 
 def pair_scratch_stats(stream=None):

@@ -77,8 +77,9 @@ struct PairState {
   Scratch call;                 // scratch of update / record / frame / digest batches
   Scratch balance;              // byte-balance region of whole-range launches (bal_words words)
   uint32_t* counter = nullptr;  // ticket counter: a 16 B slot of a shared slab, not owned
-  uint32_t hint[2] = {kNoHint, kNoHint};  // slots of the one-shot apply's pinned hint words:
-                                          // [0] update_batch, [1] round 0 of update_ordered
+  uint32_t hint[3] = {kNoHint, kNoHint, kNoHint};  // slots of the one-shot apply's pinned hint words:
+                                                   // [0] update_batch, [1] round 0 of update_ordered,
+                                                   // [2] update_cow_batch
   Side side;
 };
 
@@ -850,6 +851,8 @@ struct ApplyPlan {
   uint32_t grid = 0;
   uint64_t ptab_cap = 0;
   uint64_t* hint = nullptr;  // device view of the pair's pinned hint word
+  bool cow = false;          // hf3fs_crc_update_cow_batch: four range records per IO, always one-shot
+  const uint64_t* dst = nullptr;  // its destinations (device, may be null)
 };
 uint32_t apply_piece_shift() {
   const uint32_t kib = options().apply_piece_kib.load();
@@ -861,7 +864,16 @@ uint64_t one_shot_cap(uint64_t n, uint32_t max_len) {
   const uint64_t cap = update_piece_cap(n, max_len, apply_piece_shift());
   return options().apply_grid.load() == 0 || cap >= (1ull << 31) || cap * 4 > (1ull << 30) ? 0 : cap;
 }
-// which: the pair's hint word -- 0 update_batch's, 1 the one of update_ordered's first round.
+// The one-shot grid for n IOs from a hint word (pieces << 32 | n of the pair's previous call):
+// that call's pieces per IO with 3 % + 64 workgroups of headroom, at most cap; 0 = no call yet.
+static uint32_t hinted_grid(uint64_t h, uint64_t n, uint64_t cap) {
+  const uint64_t prev_pieces = h >> 32, prev_n = h & 0xffffffffull;
+  if (!prev_n) return 0;
+  const uint64_t want = prev_pieces * n / prev_n;
+  return (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, want + want / 32 + 64));
+}
+// which: the pair's hint word -- 0 update_batch's, 1 the one of update_ordered's first round
+// (2 is update_cow_batch's, plan_apply_cow below).
 int plan_apply(Context* c, hipStream_t s, uint64_t n, uint32_t max_len, ApplyPlan* ap, int which = 0) {
   const Options& o = options();
   ap->shift = apply_piece_shift();
@@ -872,12 +884,11 @@ int plan_apply(Context* c, hipStream_t s, uint64_t n, uint32_t max_len, ApplyPla
   const uint64_t cap = one_shot_cap(n, max_len);
   if (!cap) return HF3FS_CRC_OK;  // tickets
   const uint64_t h = __atomic_load_n(host, __ATOMIC_ACQUIRE);
-  const uint64_t prev_pieces = h >> 32, prev_n = h & 0xffffffffull;
+  const uint32_t hinted = hinted_grid(h, n, cap);
   if (mode == 2) {  // test: a small grid, every workgroup loops over several pieces
     ap->grid = (uint32_t)c->cus;
-  } else if (prev_n) {  // the previous call's pieces per IO, 3 % + 64 workgroups of headroom
-    const uint64_t want = prev_pieces * n / prev_n;
-    ap->grid = (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, want + want / 32 + 64));
+  } else if (hinted) {
+    ap->grid = hinted;
   } else if (mode < 0) {
     return HF3FS_CRC_OK;  // auto, first call of the pair: tickets (they count the pieces)
   }
@@ -968,7 +979,10 @@ static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint
     const int nt = (int)options().apply_nt.load();
     HIP_OR_FAIL(launch_update_fused(d_ios, n, max_len, type, mode, sc, c->tables, grid, nt, s));
   } else {  // three passes: prep, the pre jobs through k_crc_ranges, apply (+ finalize of most IOs)
-    HIP_OR_FAIL(launch_update_prep(d_ios, n, max_len, type, mode, sc, prep_runs, s));
+    if (ap.cow)
+      HIP_OR_FAIL(launch_update_prep_cow(d_ios, ap.dst, n, max_len, type, mode, sc, prep_runs, s));
+    else
+      HIP_OR_FAIL(launch_update_prep(d_ios, n, max_len, type, mode, sc, prep_runs, s));
     ListSource pre{sc.pre_addr, sc.pre_len, sc.pre_start, 2 * n, 0u};
     if (int rc = run_ranges_list(c, ktype, pre, max_len, sc.pre_out, s, kPreSeg, sc.ctl + kCtlPreMax, nullptr,
                                  sc.ctl + kCtlQueuePre, &runs))
@@ -982,8 +996,11 @@ static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint
       HIP_OR_FAIL(launch_update_finalize(d_ios, n, type, mode, sc, c->tables, max_len, 1, false, join.side.side));
       HIP_OR_FAIL(join.record());
     }
-    HIP_OR_FAIL(launch_update_apply(d_ios, n, max_len, type, mode, sc, c->tables, true, ap.grid,
-                                    (int)options().apply_nt.load(), ap.ptab_cap, ap.hint, s));
+    if (ap.cow)
+      HIP_OR_FAIL(launch_update_apply_cow(n, sc, ap.grid, (int)options().apply_nt.load(), ap.ptab_cap, ap.hint, s));
+    else
+      HIP_OR_FAIL(launch_update_apply(d_ios, n, max_len, type, mode, sc, c->tables, true, ap.grid,
+                                      (int)options().apply_nt.load(), ap.ptab_cap, ap.hint, s));
   }
   ListSource post{sc.post_addr, sc.post_len, sc.post_start, 2 * n, 0u};
   if (int rc = run_ranges_list(c, ktype, post, max_len, sc.post_out, s, 256 << 10, sc.ctl + kCtlPostMax, nullptr,
@@ -1074,6 +1091,76 @@ int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t 
   }
   HIP_OR_FAIL(launch_order_step(d_ios, n, max_rounds, max_rounds, os, d_info, s));
   return HF3FS_CRC_OK;
+}
+
+// hf3fs_crc_update_cow_batch pins the three-pass pipeline with the one-shot apply in both modes:
+// its range records (payload, gap, old prefix, old suffix) are the one-shot apply's, and that
+// kernel loops when the grid is short of the piece count, so no call needs the ticketed tasks.
+static void cow_geometry(const Context* c, UpdateGeom* g) {
+  g->unfused = true;
+  g->pieces = 1;  // update_scratch_bytes / _carve: 2 n (pieces + 1) = 4 n range records
+  g->piece_min = 64 << 10;
+  g->rep = std::max<uint32_t>(1, options().prehash_rep.load());
+  g->nw = (uint32_t)c->cus * kWaves * g->rep;
+}
+// Piece-table entries of the call, 0 when the table would not fit (the call is rejected).
+static uint64_t cow_cap(uint64_t n, uint32_t max_len) {
+  if (n >= (1ull << 28)) return 0;
+  const uint64_t cap = update_cow_piece_cap(n, max_len, apply_piece_shift());
+  return cap >= (1ull << 31) || cap * 4 > (1ull << 30) ? 0 : cap;
+}
+static int cow_args(uint8_t type, int mode) {
+  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
+  if (mode != HF3FS_UPDATE_MODE_REFERENCE && mode != HF3FS_UPDATE_MODE_DELTA)
+    return fail(HF3FS_CRC_INVALID_ARG, "unknown update mode %d", mode);
+  return HF3FS_CRC_OK;
+}
+
+size_t hf3fs_crc_update_cow_scratch_bytes(uint64_t n, uint32_t max_len, int mode) {
+  if (cow_args(kTypeCrc32c, mode) || n == 0) return 0;
+  const uint64_t cap = cow_cap(n, max_len);
+  if (!cap) return 0;
+  Context* c = nullptr;
+  if (get_context(&c)) return 0;
+  UpdateGeom g;
+  cow_geometry(c, &g);
+  return update_scratch_bytes(n, g.pieces, g.nw, cap);
+}
+
+// The apply of a COW call: always one-shot.  The grid: the pieces per IO of the pair's previous
+// COW call (a hint word of its own: what this call counts never sizes a plain update_batch), the
+// ticketed apply's grid before any call has counted (the one-shot kernel loops over the rest), one
+// workgroup per CU with apply_grid = 2.  ap->ptab_cap is set by the caller.
+static int plan_apply_cow(Context* c, hipStream_t s, uint64_t n, ApplyPlan* ap) {
+  ap->cow = ap->one_shot = true;
+  ap->shift = apply_piece_shift();
+  uint64_t* host = nullptr;
+  if (int rc = c->hint_word(s, 2, &host, &ap->hint)) return rc;
+  const uint32_t hinted = hinted_grid(__atomic_load_n(host, __ATOMIC_ACQUIRE), n, ap->ptab_cap);
+  ap->grid = options().apply_grid.load() == 2 ? (uint32_t)c->cus : hinted ? hinted : (uint32_t)c->cus * 8;
+  return HF3FS_CRC_OK;
+}
+
+int hf3fs_crc_update_cow_batch(uint8_t type, hf3fs_crc_update_io* d_ios, const uint64_t* d_dst, uint64_t n,
+                               uint32_t max_len, int mode, void* stream) {
+  if (int rc = cow_args(type, mode)) return rc;
+  if (n == 0) return HF3FS_CRC_OK;
+  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  ApplyPlan ap;
+  ap.dst = d_dst;
+  ap.ptab_cap = cow_cap(n, max_len);
+  if (!ap.ptab_cap)
+    return fail(HF3FS_CRC_INVALID_ARG, "piece table of %llu IOs of %u bytes exceeds 1 GiB: split the batch",
+                (unsigned long long)n, max_len);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  UpdateGeom g;
+  cow_geometry(c, &g);
+  if (int rc = plan_apply_cow(c, s, n, &ap)) return rc;
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, update_scratch_bytes(n, g.pieces, g.nw, ap.ptab_cap), &base)) return rc;
+  return update_run(c, type, d_ios, n, max_len, mode, g, ap, base, s);
 }
 
 int hf3fs_crc_pair_scratch_stats(void* stream, uint64_t* call_bytes, uint64_t* allocations) {

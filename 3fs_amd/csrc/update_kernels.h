@@ -56,7 +56,8 @@ struct UpdateScratch {
   // one-shot apply: every range is cut at 2^piece_shift-aligned destination
   // addresses; one workgroup copies one piece and exits.  tasks[2 i] / tasks[2 i + 1] are IO
   // i's payload / gap range records (verify = first piece | verify << 31), ptab[p] the
-  // record of piece p.  one_shot = 0: the ticketed tasks above.
+  // record of piece p.  one_shot = 0: the ticketed tasks above.  With destinations
+  // (k_update_prep_cow) IO i has four records, tasks[4 i + k], k as in update_plan.h plan_ranges.
   uint32_t* ptab;
   uint32_t piece_shift;
   uint32_t one_shot;
@@ -80,6 +81,9 @@ void update_scratch_carve(void* base, uint64_t n, uint32_t pieces, uint32_t piec
                           uint64_t ptab_cap, UpdateScratch* s);
 // Piece-table entries a batch of n IOs of at most max_len bytes can need (payload + gap).
 uint64_t update_piece_cap(uint64_t n, uint32_t max_len, uint32_t piece_shift);
+// The same for a batch with destinations (hf3fs_crc_update_cow_batch): payload, gap, old prefix
+// and old suffix, n * (max_len / P + 8) (update_plan.h plan_piece_bound).
+uint64_t update_cow_piece_cap(uint64_t n, uint32_t max_len, uint32_t piece_shift);
 
 // prep for every IO; with place_runs (2n <= kPrepRunJobs) one extra workgroup places the
 // byte runs of the 2n pre jobs over s.run_waves waves meanwhile (s.run_bal / s.run_boff,
@@ -89,6 +93,15 @@ constexpr uint32_t kPrepThreads = 1024;  // prep workgroup size (the runs workgr
 constexpr uint32_t kPrepIoThreads = 256;  // threads per prep workgroup deriving IOs
 hipError_t launch_update_prep(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max_len, uint8_t type, int mode,
                               const UpdateScratch& s, bool place_runs, hipStream_t st);
+// hf3fs_crc_update_cow_batch's prep and apply (one-shot only; s.one_shot = 1, s.tasks holds 4 n
+// range records: update_scratch_bytes / _carve with pieces = 1).  IO i's new image is written at
+// dsts[i] unless that is 0 or the IO's chunk (dsts may be null): prep emits the payload and gap
+// records there plus, out of place, the old prefix and old suffix copied from the chunk; the
+// apply is k_update_apply_one_shot over those records (grid, ptab_cap, hint as below).
+hipError_t launch_update_prep_cow(hf3fs_crc_update_io* ios, const uint64_t* dsts, uint64_t n, uint32_t max_len,
+                                  uint8_t type, int mode, const UpdateScratch& s, bool place_runs, hipStream_t st);
+hipError_t launch_update_apply_cow(uint64_t n, const UpdateScratch& s, uint32_t grid, int nt, uint64_t ptab_cap,
+                                   uint64_t* hint, hipStream_t st);
 // Copies the verified payloads and zero-fills gaps (apply tasks).  With
 // finalize_delta, the apply workgroups also give every IO its payload verdict
 // (ChunkReplica.cc:193-207) and finalize every IO that needs no post job

@@ -15,112 +15,12 @@
 
 
 #include "crc_device.h"
+#include "update_plan.h"  // Eff / derive, the apply's ranges and piece cuts (plain C++, also built on the CPU)
 
 #include <algorithm>
 
 namespace hf3fs_crc {
 namespace {
-
-struct Eff {
-  uint32_t s0, s1;          // chunk size before / after
-  uint32_t off, len;        // the UpdateIO as updateChecksum sees it (truncate: off = size, len = 0)
-  uint32_t wval, cval;      // write / chunk checksum values
-  uint32_t zero_from, zero_to;
-  uint8_t wtype, ctype;
-  uint8_t kase;             // 1 none/empty, 2 reuse, 3 append-combine, 4 recompute
-  bool delta;               // case 4 via the delta identity
-  bool verify;              // payload checksum must be verified
-  bool te;                  // truncate / extend
-  bool ok;                  // IO is well formed
-  bool engine;              // chunk-engine semantics (HF3FS_UPDATE_FLAG_ENGINE)
-  bool hash_payload;        // the payload job must run (verify, or engine without_checksum)
-};
-
-__device__ __forceinline__ Eff derive(const hf3fs_crc_update_io& io, uint32_t max_len, uint8_t type, int mode) {
-  Eff e{};
-  e.s0 = io.chunk_size;
-  e.ctype = io.chunk_checksum_type;
-  e.cval = io.chunk_checksum;
-  e.ok = true;
-  e.zero_from = e.zero_to = 0;
-  // The batch hashes bytes in `type`: a write's payload and (when the types differ)
-  // its prefix / suffix recompute, ChunkReplica.cc:340,356-392 -- the chunk's stored
-  // type may differ for a write; a truncate / extend hashes in the chunk's type.
-  if (io.chunk_size > max_len || e.ctype > kTypeCrc32) e.ok = false;
-  if (io.update_type != HF3FS_UPDATE_WRITE && e.ctype != kTypeNone && e.ctype != type) e.ok = false;
-  if (io.update_type == HF3FS_UPDATE_WRITE) {
-    // ChunkReplica.cc:139-145: offset >= chunkSize || offset + length > chunkSize -> kInvalidArg
-    if (io.offset >= max_len || (uint64_t)io.offset + io.length > max_len) e.ok = false;
-    if (io.length && !io.payload) e.ok = false;
-    if (io.write_checksum_type != kTypeNone && io.write_checksum_type != type) e.ok = false;
-    e.off = io.offset;
-    e.len = io.length;
-    e.s1 = e.s0 > io.offset + io.length ? e.s0 : io.offset + io.length;
-    if (io.offset > e.s0) {
-      e.zero_from = e.s0;
-      e.zero_to = io.offset;
-    }
-    e.wtype = io.write_checksum_type;
-    e.wval = io.write_checksum;
-    e.verify = e.wtype != kTypeNone && e.len != 0;
-  } else if (io.update_type == HF3FS_UPDATE_TRUNCATE || io.update_type == HF3FS_UPDATE_EXTEND) {
-    const uint32_t target = io.length;  // ChunkReplica.cc:255-269
-    if (target > max_len) e.ok = false;
-    if (target <= e.s0) {
-      e.s1 = io.update_type == HF3FS_UPDATE_TRUNCATE ? target : e.s0;
-    } else {
-      e.s1 = target;
-      e.zero_from = e.s0;
-      e.zero_to = target;
-    }
-    e.te = true;
-    e.wtype = e.ctype;  // create(meta.checksumType, nullptr, 0) (:328-332)
-    e.wval = e.ctype == kTypeNone ? 0u : ~0u;
-    e.off = e.s1;
-    e.len = 0;
-  } else {
-    e.ok = false;
-  }
-  e.hash_payload = e.verify;
-  const bool is_append = io.offset == e.s0;  // :243, before the write
-  if (io.flags & HF3FS_UPDATE_FLAG_ENGINE) {
-    // ChunkEngine.cc:41-45: a CRC32C write checksum is verified (engine.rs:297-311), anything else
-    // is "without_checksum" -- hashed and used.  The stored checksum is always the CRC32C of the
-    // chunk bytes (chunk.rs:89-281), an empty chunk included (~0 raw).
-    e.engine = true;
-    if (type != kTypeCrc32c) e.ok = false;
-    e.ctype = kTypeCrc32c;
-    if (e.s0 == 0) e.cval = ~0u;
-    if (!e.te) {
-      e.verify = io.write_checksum_type == kTypeCrc32c && e.len != 0;
-      e.hash_payload = e.len != 0;
-      if (e.wtype != kTypeCrc32c) e.ok = e.ok && io.write_checksum_type == kTypeNone;
-    }
-    e.wtype = kTypeCrc32c;
-    if (e.te) e.wval = ~0u;
-    if (e.s1 == 0)
-      e.kase = 1;
-    else if (e.off == 0 && e.len == e.s1)
-      e.kase = 2;  // copy_on_write skip_read: reuse (chunk.rs:110,150-155)
-    else if (e.s0 > 0 && is_append)
-      e.kase = 3;  // direct / indirect append: combine (chunk.rs:229,266)
-    else
-      e.kase = 4;
-    e.delta = e.kase == 4 && mode == HF3FS_UPDATE_MODE_DELTA;
-    return e;
-  }
-  const bool combine = e.s0 > 0 && is_append;
-  if (e.wtype == kTypeNone || e.s1 == 0)
-    e.kase = 1;
-  else if (e.off == 0 && e.len == e.s1)
-    e.kase = 2;
-  else if (e.wtype == e.ctype && combine)
-    e.kase = 3;
-  else
-    e.kase = 4;
-  e.delta = e.kase == 4 && mode == HF3FS_UPDATE_MODE_DELTA && (e.s0 == 0 || e.ctype == e.wtype);
-  return e;
-}
 
 template <uint32_t POLY>
 __device__ __forceinline__ uint32_t xpow8(int64_t nbytes, const PolyTables* T) {
@@ -179,6 +79,7 @@ __device__ __forceinline__ uint32_t ck_combine_m(uint32_t a, uint32_t b, uint32_
 // the path Chunk::copy_on_write / safe_write takes (chunk.rs:89-281, capacity = max_len).
 __device__ __forceinline__ uint8_t ck_case(const hf3fs_crc_update_io& io, const Eff& e) {
   if (!e.engine) return e.kase;
+  if (e.sync) return HF3FS_CKCASE_REUSE;  // is_syncing: copy_on_write with skip_read (chunk.rs:112,152-170)
   const uint32_t s0 = io.chunk_size;
   if (e.te) {  // the bridge's truncate / extend: safe_write(no data, offset = target, truncate)
     const uint32_t target = io.length;
@@ -208,11 +109,16 @@ __device__ __forceinline__ void pre_lens(const Eff& e, uint64_t& l0, uint64_t& l
 // (payload; old bytes for the delta method) and the "post" jobs (prefix +
 // suffix after the write, reference algorithm).  Returns the derived IO and the
 // longest pre / post job in pre_max / post_max (the caller raises ctl's maxima).
+// COW (hf3fs_crc_update_cow_batch): the IO's new image is written at `image`, not at io.chunk.
+// The pre jobs still read io.chunk (DELTA's old bytes are the committed version's); the post
+// jobs read the new image, where the prefix holds the zero-filled gap of a write past the size.
+template <bool COW = false>
 __device__ __forceinline__ Eff prep_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i, uint32_t max_len,
                                         uint8_t type, int mode, const UpdateScratch& s, uint32_t& pre_max,
-                                        uint32_t& post_max) {
+                                        uint32_t& post_max, uint64_t image = 0) {
   const hf3fs_crc_update_io io = ios[i];
   const Eff e = derive(io, max_len, type, mode);
+  const uint64_t written = COW ? image : io.chunk;
   // only the output fields are stored: the prep launch's runs workgroup reads the input
   // fields of the same records meanwhile (bal_runs_block), so they are never rewritten
   ios[i].status = e.ok ? HF3FS_CRC_OK : HF3FS_CRC_INVALID_ARG;
@@ -227,9 +133,9 @@ __device__ __forceinline__ Eff prep_one(hf3fs_crc_update_io* __restrict__ ios, u
   if (e.ok) {
     if (e.kase == 4 && !e.delta) {  // reference: prefix + suffix after the write
       const uint32_t suffix_start = e.off + e.len < e.s1 ? e.off + e.len : e.s1;
-      pa = io.chunk;
+      pa = written;
       pl = e.off;
-      sa = io.chunk + suffix_start;
+      sa = written + suffix_start;
       sl = e.s1 - suffix_start;
     }
   }
@@ -275,13 +181,6 @@ __device__ __forceinline__ void piece_bounds(uint64_t dst, uint64_t len, uint32_
   b = b0 < len ? b0 : len;
 }
 
-// One-shot apply pieces of a range: cut at every 2^shift-aligned destination address.
-__device__ __forceinline__ uint32_t pieces_of(uint64_t dst, uint64_t len, uint32_t shift) {
-  if (!len) return 0;
-  const uint64_t m = (uint64_t(1) << shift) - 1;
-  return (uint32_t)(((dst & m) + len + m) >> shift);
-}
-
 // Byte runs of the 2n pre jobs over nw waves, by ONE extra workgroup of the prep launch
 // (k_bal_assign's boff form, crc_kernels.hip): wave k starts at byte X_k = ceil(k T / nw)
 // of the jobs laid end to end (T their total), i.e. at byte boff[k] of job bal[k];
@@ -293,7 +192,9 @@ __device__ __forceinline__ uint32_t pieces_of(uint64_t dst, uint64_t len, uint32
 // wave scan and one LDS step over the wave totals give every thread its byte prefix.
 constexpr uint32_t kRunIos = kPrepRunJobs / 2 / kPrepThreads;
 static_assert(kRunIos * 2 * kPrepThreads == kPrepRunJobs, "runs workgroup geometry");
-__device__ void bal_runs_block(const hf3fs_crc_update_io* __restrict__ ios, uint32_t n, uint32_t max_len,
+// (forced inline: both prep kernels run it, and called out of line its uniform arguments would
+// travel in vector registers)
+__device__ __forceinline__ void bal_runs_block(const hf3fs_crc_update_io* __restrict__ ios, uint32_t n, uint32_t max_len,
                                uint8_t type, int mode, uint32_t nw, uint32_t* __restrict__ bal,
                                uint64_t* __restrict__ boff) {
   __shared__ uint64_t s_wave[kPrepThreads / 64];
@@ -463,6 +364,74 @@ __global__ __launch_bounds__(kPrepThreads) void k_update_prep(hf3fs_crc_update_i
     }
   }
   // the launch's extra workgroup (place_runs): the pre hash's byte runs
+  if (place_runs && blockIdx.x == gridDim.x - 1)
+    bal_runs_block(ios, (uint32_t)n, max_len, type, mode, s.run_waves, s.run_bal, s.run_boff);
+}
+
+// prep of hf3fs_crc_update_cow_batch (one-shot apply only): as k_update_prep, with IO i's image
+// written at plan_image(chunk, dsts[i]) and kPlanRanges range records per IO at tasks[4 i + k]
+// (update_plan.h plan_ranges: payload, gap, old prefix, old suffix).  Every record carries the
+// IO's verify bit -- a failed payload verify copies no old byte either -- and ptab[p] is the
+// record of piece p, an IO's pieces in record order.  dsts may be null (every IO in place).
+__global__ __launch_bounds__(kPrepThreads) void k_update_prep_cow(hf3fs_crc_update_io* __restrict__ ios,
+                                                                  const uint64_t* __restrict__ dsts, uint64_t n,
+                                                                  uint32_t max_len, uint8_t type, int mode,
+                                                                  UpdateScratch s, int place_runs) {
+  const uint32_t lane = threadIdx.x & 63;
+  unsigned long long* pieces = reinterpret_cast<unsigned long long*>(s.ctl + kCtlPieces);
+  for (uint64_t i0 = (uint64_t)blockIdx.x * kPrepIoThreads + (threadIdx.x & ~63u);
+       threadIdx.x < kPrepIoThreads && i0 < n; i0 += (uint64_t)gridDim.x * kPrepIoThreads) {
+    const uint64_t i = i0 + lane;
+    PlanRange R[kPlanRanges] = {};
+    uint32_t wval = 0, verify = 0, pre_max = 0, post_max = 0;
+    if (i < n) {
+      const hf3fs_crc_update_io io = ios[i];
+      const uint64_t image = plan_image(io.chunk, dsts ? dsts[i] : 0);
+      const Eff e = prep_one<true>(ios, i, max_len, type, mode, s, pre_max, post_max, image);
+      plan_ranges(io, e, image, R);
+      if (e.ok) {
+        wval = e.wval;
+        verify = e.verify;
+      }
+    }
+    uint32_t before[kPlanRanges + 1];  // pieces of the IO's earlier ranges
+    before[0] = 0;
+#pragma unroll
+    for (int k = 0; k < kPlanRanges; ++k) before[k + 1] = before[k] + pieces_of(R[k].dst, R[k].len, s.piece_shift);
+    const uint32_t cnt_io = before[kPlanRanges];
+    uint32_t incl = cnt_io;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t y = __shfl_up(incl, d);
+      if (lane >= (uint32_t)d) incl += y;
+      pre_max = max(pre_max, (uint32_t)__shfl_xor(pre_max, d));
+      post_max = max(post_max, (uint32_t)__shfl_xor(post_max, d));
+    }
+    if (lane == 0 && pre_max) atomicMax(&s.ctl[kCtlPreMax], pre_max);
+    if (lane == 0 && post_max) atomicMax(&s.ctl[kCtlPostMax], post_max);
+    const uint32_t total = __shfl(incl, 63);
+    unsigned long long base = 0;
+    if (lane == 63 && total) base = atomicAdd(pieces, (unsigned long long)total);
+    base = __shfl(base, 63);
+    const uint64_t at = base + incl - cnt_io;
+    if (i < n) {
+#pragma unroll
+      for (int k = 0; k < kPlanRanges; ++k)
+        s.tasks[kPlanRanges * i + k] =
+            ApplyTask{R[k].dst, R[k].src, R[k].len, (uint32_t)i, wval, (uint32_t)(at + before[k]) | (verify << 31)};
+    }
+    for (uint32_t l = 0; l < 64; ++l) {  // wave-uniform: one IO's table rows at a time, coalesced
+      const uint32_t cnt = __builtin_amdgcn_readlane(cnt_io, l);
+      if (!cnt) continue;
+      const uint32_t b1 = __builtin_amdgcn_readlane(before[1], l), b2 = __builtin_amdgcn_readlane(before[2], l),
+                     b3 = __builtin_amdgcn_readlane(before[3], l);
+      const uint64_t atl = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)at, l) |
+                           (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(at >> 32), l) << 32;
+      const uint32_t r = (uint32_t)(kPlanRanges * (i0 + l));
+      for (uint32_t j = lane; j < cnt; j += 64)
+        s.ptab[atl + j] = r + (j >= b1 ? 1u : 0u) + (j >= b2 ? 1u : 0u) + (j >= b3 ? 1u : 0u);
+    }
+  }
   if (place_runs && blockIdx.x == gridDim.x - 1)
     bal_runs_block(ios, (uint32_t)n, max_len, type, mode, s.run_waves, s.run_bal, s.run_boff);
 }
@@ -781,13 +750,12 @@ __device__ __forceinline__ void store_hint(uint64_t* hint, uint64_t np, uint64_t
 template <int PSHIFT, bool NTL, bool NTS>
 __device__ __forceinline__ void one_shot_piece(uint64_t b, uint32_t r, const ApplyTask* __restrict__ tasks,
                                                const uint32_t* __restrict__ pre_out) {
-  constexpr uint64_t P = uint64_t(1) << PSHIFT;
   constexpr int G = 1 << (PSHIFT - 12);  // granules per thread (256 threads x 16 B)
   const uint32_t tid = threadIdx.x;
   const ApplyTask R = tasks[r];
   const uint32_t first = R.verify & 0x7fffffffu;
-  const uint64_t cut = (R.dst & ~(P - 1)) + ((b - first) << PSHIFT);
-  const uint64_t a = cut > R.dst ? cut : R.dst, e = cut + P < R.dst + R.len ? cut + P : R.dst + R.len;
+  uint64_t a, e;  // the piece's destination bytes (update_plan.h)
+  piece_span(R.dst, R.len, PSHIFT, b - first, a, e);
   const int64_t so = (int64_t)(R.src - R.dst);  // source offset (R.src == 0: zero fill)
   const uint64_t ga = (a + 15) & ~uint64_t(15), ge = e & ~uint64_t(15);
   // edge bytes (at most 30, only in a range's first / last piece), one per thread
@@ -819,7 +787,8 @@ __device__ __forceinline__ void one_shot_piece(uint64_t b, uint32_t r, const App
   }
 }
 
-template <int PSHIFT, bool NTL, bool NTS>
+// RPI: range records per IO -- 2 (payload, gap) in place, kPlanRanges with destinations.
+template <int PSHIFT, bool NTL, bool NTS, uint32_t RPI = 2>
 __global__ __launch_bounds__(256) void k_update_apply_one_shot(const ApplyTask* __restrict__ tasks,
                                                                const uint32_t* __restrict__ ptab,
                                                                const uint32_t* __restrict__ pre_out,
@@ -833,7 +802,7 @@ __global__ __launch_bounds__(256) void k_update_apply_one_shot(const ApplyTask* 
   const uint32_t r = b < ptab_cap ? ptab[b] : 0u;  // (entries past the count: never used)
   if (hint && b == 0 && threadIdx.x == 0) store_hint(hint, npieces, n);
   if (b >= npieces) return;
-  one_shot_piece<PSHIFT, NTL, NTS>(b, r < 2 * n ? r : 0u, tasks, pre_out);
+  one_shot_piece<PSHIFT, NTL, NTS>(b, r < RPI * n ? r : 0u, tasks, pre_out);
   for (uint64_t c = b + gridDim.x; c < npieces; c += gridDim.x)  // a grid short of the count
     one_shot_piece<PSHIFT, NTL, NTS>(c, ptab[c], tasks, pre_out);
 }
@@ -1058,6 +1027,11 @@ uint64_t update_piece_cap(uint64_t n, uint32_t max_len, uint32_t piece_shift) {
   return n * (((uint64_t)max_len >> piece_shift) + 4);
 }
 
+uint64_t update_cow_piece_cap(uint64_t n, uint32_t max_len, uint32_t piece_shift) {
+  // payload, gap, old prefix and old suffix of one IO are disjoint inside [0, max_len)
+  return n * plan_piece_bound(max_len, piece_shift, kPlanRanges);
+}
+
 size_t update_scratch_bytes(uint64_t n, uint32_t pieces, uint32_t nw, uint64_t ptab_cap) {
   const uint64_t tasks = n * 2 * (uint64_t)(pieces + 1);
   const uint64_t runs = kRunBlocksMax * 8 + (nw + 1) * (4 + 8);
@@ -1109,6 +1083,44 @@ hipError_t launch_update_prep(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max
   return hipGetLastError();
 }
 
+hipError_t launch_update_prep_cow(hf3fs_crc_update_io* ios, const uint64_t* dsts, uint64_t n, uint32_t max_len,
+                                  uint8_t type, int mode, const UpdateScratch& s, bool place_runs, hipStream_t st) {
+  const uint64_t want = (n + kPrepIoThreads - 1) / kPrepIoThreads;
+  const unsigned grid = (unsigned)(want < 1024 ? (want ? want : 1) : 1024);
+  hipLaunchKernelGGL(k_update_prep_cow, dim3(grid + (place_runs ? 1 : 0)), dim3(kPrepThreads), 0, st, ios, dsts, n,
+                     max_len, type, mode, s, place_runs ? 1 : 0);
+  return hipGetLastError();
+}
+
+// The one-shot apply over RPI range records per IO (2 in place, kPlanRanges with destinations).
+// nt bit 0: non-temporal payload loads; stores always non-temporal (the probe's best).
+template <uint32_t RPI>
+static void launch_one_shot(uint64_t n, const UpdateScratch& s, uint32_t grid, int nt, uint64_t ptab_cap,
+                            uint64_t* hint, hipStream_t st) {
+  const uint64_t* count = reinterpret_cast<const uint64_t*>(s.ctl + kCtlPieces);
+#define HF3FS_ONE_SHOT(SH)                                                                                  \
+  do {                                                                                                      \
+    if (nt & 1)                                                                                             \
+      hipLaunchKernelGGL((k_update_apply_one_shot<SH, true, true, RPI>), dim3(grid), dim3(256), 0, st,       \
+                         s.tasks, s.ptab, s.pre_out, count, n, ptab_cap, hint);                             \
+    else                                                                                                    \
+      hipLaunchKernelGGL((k_update_apply_one_shot<SH, false, true, RPI>), dim3(grid), dim3(256), 0, st,      \
+                         s.tasks, s.ptab, s.pre_out, count, n, ptab_cap, hint);                             \
+  } while (0)
+  switch (s.piece_shift) {
+    case 12: HF3FS_ONE_SHOT(12); break;
+    case 14: HF3FS_ONE_SHOT(14); break;
+    default: HF3FS_ONE_SHOT(13);
+  }
+#undef HF3FS_ONE_SHOT
+}
+
+hipError_t launch_update_apply_cow(uint64_t n, const UpdateScratch& s, uint32_t grid, int nt, uint64_t ptab_cap,
+                                   uint64_t* hint, hipStream_t st) {
+  launch_one_shot<kPlanRanges>(n, s, grid, nt, ptab_cap, hint, st);
+  return hipGetLastError();
+}
+
 hipError_t launch_update_apply(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max_len, uint8_t type, int mode,
                                const UpdateScratch& s, const DeviceTables* tabs, bool finalize_delta, uint32_t grid,
                                int nt, uint64_t ptab_cap, uint64_t* hint, hipStream_t st) {
@@ -1133,23 +1145,8 @@ hipError_t launch_update_apply(hf3fs_crc_update_io* ios, uint64_t n, uint32_t ma
     case 7: HF3FS_APPLY(P, true, true, true); break;    \
     default: HF3FS_APPLY(P, false, false, false);       \
   }
-  if (s.one_shot) {  // nt bit 0: non-temporal payload loads; stores always non-temporal (the probe's best)
-    const uint64_t* count = reinterpret_cast<const uint64_t*>(s.ctl + kCtlPieces);
-#define HF3FS_ONE_SHOT(SH)                                                                                     \
-  do {                                                                                                         \
-    if (nt & 1)                                                                                                \
-      hipLaunchKernelGGL((k_update_apply_one_shot<SH, true, true>), dim3(grid), dim3(256), 0, st, s.tasks,      \
-                         s.ptab, s.pre_out, count, n, ptab_cap, hint);                                         \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_update_apply_one_shot<SH, false, true>), dim3(grid), dim3(256), 0, st, s.tasks,     \
-                         s.ptab, s.pre_out, count, n, ptab_cap, hint);                                         \
-  } while (0)
-    switch (s.piece_shift) {
-      case 12: HF3FS_ONE_SHOT(12); break;
-      case 14: HF3FS_ONE_SHOT(14); break;
-      default: HF3FS_ONE_SHOT(13);
-    }
-#undef HF3FS_ONE_SHOT
+  if (s.one_shot) {
+    launch_one_shot<2>(n, s, grid, nt, ptab_cap, hint, st);
   } else if (type == kTypeCrc32) {
     HF3FS_APPLY_NT(kPolyCrc32)
   } else {

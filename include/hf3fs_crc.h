@@ -266,7 +266,21 @@ enum {
    * always CRC32C and always the CRC of the chunk bytes (an empty chunk is ~0 raw = 0 finalized); a write
    * whose checksum type is not CRC32C is taken "without_checksum" (hashed, not verified).  Values stay
    * raw at this ABI, as at the C++ bridge (finalized = ~raw, ChunkEngine.cc:42,66). */
-  HF3FS_UPDATE_FLAG_ENGINE = 1
+  HF3FS_UPDATE_FLAG_ENGINE = 1,
+  /* A resync write (UpdateIO.isSyncing): the forwarded whole chunk replaces the
+   * replica's.  Valid only on a WRITE with offset == 0 -- the one shape resync produces
+   * (ReliableForwarding.cc:179-206 reads the whole chunk); at any other offset the engine would write
+   * stale thread-buffer bytes and the replica a size smaller than the write's end, so any other use
+   * (offset != 0, truncate, extend) is kInvalidArg for that IO.  Honoured by hf3fs_crc_update_batch,
+   * _update_ordered and _update_cow_batch alike; records with the bit clear behave as before.
+   * Replica IOs: the payload verify is as usual, out_size = length (ChunkReplica.cc:289), and the
+   * checksum follows updateChecksum with that size (:334-339,392): a write of type NONE or length 0
+   * gives case NONE, value 0 and the write's type, every other REUSE of the write checksum.
+   * Engine IOs: out_size = length, the checksum is the payload's CRC32C (verified when the write is
+   * typed CRC32C, hashed otherwise), the case REUSE: copy_on_write with skip_read (chunk.rs:112,
+   * 152-170; engine.rs:378-386).  Nothing is read from the old chunk in either form, and no byte at
+   * or beyond `length` is written (in place: the old bytes there stay, outside the new size). */
+  HF3FS_UPDATE_FLAG_SYNCING = 2
 };
 
 /* Applies n IOs to n DISTINCT chunks: verify the payload checksum
@@ -346,6 +360,48 @@ int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io *d_ios, uint64_t 
  * call of the largest (n, max_len, max_rounds) of a mode, no later call on the pair grows the
  * buffer.  0 for arguments the call would reject. */
 size_t hf3fs_crc_update_ordered_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds);
+/* hf3fs_crc_update_batch with a destination per IO: Chunk::copy_on_write (chunk_engine/src/alloc/
+ * chunk.rs:89-174), which writes the new version of a chunk into a newly allocated one and leaves
+ * the committed version readable.  d_dst is a device array of n destination addresses, or NULL.
+ * In place: d_dst == NULL, d_dst[i] == 0 or d_dst[i] == d_ios[i].chunk applies IO i exactly as
+ * hf3fs_crc_update_batch does; with d_dst == NULL the call writes byte for byte what update_batch
+ * writes, into the records and into the chunks.  The error returns match too (unknown type or mode,
+ * null d_ios with n > 0 -> kInvalidArg, n == 0 -> OK; all checked before any device is touched);
+ * one more: a batch whose piece table (below) would pass 1 GiB is kInvalidArg -- split it.
+ * Out of place (any other d_dst[i]): for an IO whose status comes back OK, dst[0, out_size) becomes
+ * the chunk image the reference leaves -- the old bytes outside the write, the gap zero-fill, the
+ * payload, the zero extension of an extend; a shortening truncate copies [0, target).  This holds
+ * for every OK IO, also one that changes no byte (a zero-length write, a truncate to the current
+ * size).  No byte of `chunk` is written and no byte of dst at or beyond out_size (the engine's
+ * 512-byte write padding is not modelled).  An IO that fails (_CHECKSUM_MISMATCH, _INVALID_ARG,
+ * _DEVICE_ERROR) leaves chunk and dst untouched.  Every output field and checksum_case have the
+ * values the in-place call gives for the same IO, in both modes.  On commit the caller swaps the
+ * chunk address for the destination.
+ * Aliasing: dst has capacity >= max(chunk_size, offset + length) and overlaps no chunk, payload,
+ * record or other destination of the batch; anything else is undefined, as for update_batch.
+ * Pipeline: pinned in both modes to the three passes (prep, pre hash, apply) with the one-shot
+ * apply: prep emits up to four self-describing range records per IO -- payload, gap, old prefix
+ * [0, min(offset, size)), old suffix [min(offset + length, size), size); truncate / extend
+ * [0, min(size, new size)) -- and one workgroup copies one piece of one range.  DELTA hashes the old
+ * bytes under the write from `chunk`; REFERENCE hashes prefix and suffix from the new image in dst.
+ * Options honoured: apply_piece_kib (4|8|16), apply_nt bit 0 (non-temporal loads), apply_grid = 2
+ * (one workgroup per CU, each looping over pieces; any other value sizes the grid from the pair's
+ * previous COW call, the first call from the CU count), prehash_rep, audit, debug, poison, fault_io.
+ * Ignored: update_pipeline, apply_pieces, apply_min_kib, apply_nt bits 1-2, apply_grid = 0 (there
+ * is no ticketed form).  The grid hint word is the call's own: plain update_batch calls on the same
+ * (stream, thread) pair plan as if no COW call had run.
+ * Stream behaviour follows update_batch: asynchronous, capturable (also as the process's first
+ * library call), no host readback; scratch per (stream, thread) pair outside a capture and
+ * graph-owned inside one, never the stream-ordered pool; every scratch word read is written by the
+ * call first (option poison). */
+int hf3fs_crc_update_cow_batch(uint8_t type, hf3fs_crc_update_io *d_ios, const uint64_t *d_dst, uint64_t n,
+                               uint32_t max_len, int mode, void *stream);
+/* Bytes of scratch one such call takes, piece table included: after one call of the largest
+ * (n, max_len) nothing grows.  The table holds one 4-byte entry per piece of P = apply_piece_kib
+ * bytes.  A range of L bytes at any address has at most floor((L + 2 P - 2) / P) <= L / P + 2
+ * pieces, and the (at most four) ranges of an IO are disjoint inside [0, max_len), so an IO takes
+ * at most max_len / P + 8 entries: n * (max_len / P + 8) in all.  0 for arguments the call rejects. */
+size_t hf3fs_crc_update_cow_scratch_bytes(uint64_t n, uint32_t max_len, int mode);
 /* Test aid: *call_bytes = bytes of the calling (stream, thread) pair's call scratch (0: none yet),
  * *allocations = allocations and growths of pair buffers in this process so far; either may be NULL. */
 int hf3fs_crc_pair_scratch_stats(void *stream, uint64_t *call_bytes, uint64_t *allocations);
