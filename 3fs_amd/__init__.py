@@ -15,4 +15,10 @@ from ._lib import (CHECKSUM_MISMATCH, CRC32, CRC32C, DEVICE_ERROR, FLAG_ENGINE, 
                    INVALID_ARG, MODE_DELTA, MODE_REFERENCE, NONE, NOT_APPLIED, OK, UPDATE_EXTEND,
                    UPDATE_TRUNCATE, UPDATE_WRITE, Hf3fsCrcError, UpdateIO, load, update_cow,
                    update_cow_scratch_bytes, update_ordered, update_ordered_scratch_bytes)
+from ._lib import (SYNC_CHAIN_VER_LOW, SYNC_CHAIN_WRITING, SYNC_CHAIN_WRITING_CHECKSUM,  # noqa: F401
+                   SYNC_CHECKSUM_MISMATCH, SYNC_COMMIT_VER_MISMATCH, SYNC_DUPLICATE, SYNC_EQUAL,
+                   SYNC_FULL_SYNC_HEAVY, SYNC_HEAVY, SYNC_INFO_NAMES, SYNC_INFO_WORDS, SYNC_LOCAL_RECYCLING,
+                   SYNC_LOCAL_UNCOMMITTED, SYNC_MATCHED, SYNC_NONE, SYNC_REMOTE_CHAIN_VER_HIGH, SYNC_REMOTE_MISS,
+                   SYNC_REMOTE_ONLY, SYNC_REMOTE_UNCOMMITTED, SyncMeta, sync_plan, sync_plan_scratch_bytes,
+                   sync_scrub_fill)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

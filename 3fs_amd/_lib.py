@@ -124,6 +124,40 @@ class ScrubIO(ctypes.Structure):
     ]
 
 
+class SyncMeta(ctypes.Structure):
+    """hf3fs_crc_sync_meta: one chunk's metadata in the local or the remote table of a resync plan."""
+    _fields_ = [
+        ("id_hi", ctypes.c_uint64),
+        ("id_lo", ctypes.c_uint64),
+        ("chain_ver", ctypes.c_uint32),
+        ("update_ver", ctypes.c_uint32),
+        ("commit_ver", ctypes.c_uint32),
+        ("checksum", ctypes.c_uint32),
+        ("length", ctypes.c_uint32),
+        ("chunk_size", ctypes.c_uint32),
+        ("chunk_state", ctypes.c_uint8),
+        ("recycle_state", ctypes.c_uint8),
+        ("checksum_type", ctypes.c_uint8),
+        ("out_class", ctypes.c_uint8),
+        ("out_peer", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(SyncMeta) == 48
+# SyncMeta.out_class (HF3FS_SYNC_*): remote records 1-12, local records 16-18
+(SYNC_REMOTE_ONLY, SYNC_LOCAL_RECYCLING, SYNC_CHAIN_VER_LOW, SYNC_REMOTE_UNCOMMITTED, SYNC_REMOTE_CHAIN_VER_HIGH,
+ SYNC_LOCAL_UNCOMMITTED, SYNC_COMMIT_VER_MISMATCH, SYNC_CHAIN_WRITING, SYNC_FULL_SYNC_HEAVY, SYNC_CHECKSUM_MISMATCH,
+ SYNC_CHAIN_WRITING_CHECKSUM, SYNC_EQUAL) = range(1, 13)
+SYNC_MATCHED, SYNC_REMOTE_MISS, SYNC_DUPLICATE = 16, 17, 18
+SYNC_HEAVY = 1  # hf3fs_crc_sync_plan flags
+SYNC_NONE = 0xFFFFFFFF  # no peer / no fatal record
+SYNC_INFO_WORDS = 16
+# words of d_info (HF3FS_SYNC_INFO_*), in order
+SYNC_INFO_NAMES = ("fatal", "first_fatal", "n_write", "n_remove", "recycle", "chain_ver_low", "remote_uncommitted",
+                   "chain_ver_high", "local_uncommitted", "commit_ver_mismatch", "chain_writing", "full_sync_heavy",
+                   "full_sync_light", "skip", "remote_miss", "duplicates")
+
+
 class Frame(ctypes.Structure):
     """hf3fs_crc_frame: one serde message of a receive buffer."""
     _fields_ = [
@@ -231,6 +265,9 @@ SIGNATURES = {
     "hf3fs_crc_create_host": (_int, [_u8, _vp, _vp, _vp, _vp, _u64]),
     "hf3fs_crc_fill_synth": (_int, [_vp, _u64, _u64, _u64, _u64, _u64, _vp]),
     "hf3fs_crc_scrub_batch": (_int, [_u8, _vp, _u64, _u32, _vp, _vp]),
+    "hf3fs_crc_sync_plan": (_int, [_vp, _u64, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "hf3fs_crc_sync_plan_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
+    "hf3fs_crc_sync_scrub_fill": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "hf3fs_crc_engine_meta_decode": (_int, [_vp, _u64, ctypes.POINTER(EngineMeta), ctypes.POINTER(_u64)]),
     "hf3fs_crc_engine_meta_encode": (_int, [ctypes.POINTER(EngineMeta), _vp, _u64, ctypes.POINTER(_u64)]),
     "hf3fs_crc_default_etag": (_u32, [_u32, _vp]),
@@ -449,6 +486,25 @@ def file_digest_batch(blocks, file_off, out, n_files, max_blocks, stream=None, f
 def scrub_batch(ctype, ios, n, max_len, count, stream=None):
     """ios: device array of hf3fs_crc_scrub_io (updated in place); count: device u32."""
     return check(load().hf3fs_crc_scrub_batch(ctype, _p(ios), n, max_len, _p(count), _s(stream)))
+
+
+def sync_plan(local, n_local, remote, n_remote, chain_ver, info, write=None, remove=None, flags=0, stream=None):
+    """hf3fs_crc_sync_plan: local / remote are device arrays of hf3fs_crc_sync_meta (out_class and
+    out_peer updated in place), info SYNC_INFO_WORDS device u32, write / remove device u32 lists of
+    capacity n_local / n_remote (either may be None)."""
+    return check(load().hf3fs_crc_sync_plan(_p(local), n_local, _p(remote), n_remote, chain_ver, flags, _p(write),
+                                            _p(remove), _p(info), _s(stream)))
+
+
+def sync_plan_scratch_bytes(n_local, n_remote):
+    """Bytes of library-owned scratch one sync_plan of this shape takes (0: rejected counts)."""
+    return int(load().hf3fs_crc_sync_plan_scratch_bytes(n_local, n_remote))
+
+
+def sync_scrub_fill(local, addrs, write, info, n_local, scrub, stream=None):
+    """hf3fs_crc_sync_scrub_fill: n_local hf3fs_crc_scrub_io records from a plan's write list."""
+    return check(load().hf3fs_crc_sync_scrub_fill(_p(local), _p(addrs), _p(write), _p(info), n_local, _p(scrub),
+                                                  _s(stream)))
 
 
 def frame_verify_batch(buf, frames, n, max_size, count, stream=None):

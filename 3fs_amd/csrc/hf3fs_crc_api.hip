@@ -28,6 +28,7 @@
 #include "internal.h"
 #include "options.h"
 #include "order_kernels.h"
+#include "sync_kernels.h"
 #include "update_kernels.h"
 
 static_assert(sizeof(hf3fs_crc_update_io) == 56, "hf3fs_crc_update_io ABI layout");
@@ -35,6 +36,7 @@ static_assert(sizeof(hf3fs_crc_read_io) == 48, "hf3fs_crc_read_io ABI layout");
 static_assert(sizeof(hf3fs_crc_block_digest) == 24, "hf3fs_crc_block_digest ABI layout");
 static_assert(sizeof(hf3fs_crc_file_digest) == 24, "hf3fs_crc_file_digest ABI layout");
 static_assert(sizeof(hf3fs_crc_scrub_io) == 32, "hf3fs_crc_scrub_io ABI layout");
+static_assert(sizeof(hf3fs_crc_sync_meta) == 48, "hf3fs_crc_sync_meta ABI layout");
 static_assert(sizeof(hf3fs_crc_frame) == 24, "hf3fs_crc_frame ABI layout");
 static_assert(sizeof(hf3fs_crc_engine_meta) == 120, "hf3fs_crc_engine_meta ABI layout");
 static_assert(sizeof(hf3fs_crc_anomaly) == 72, "hf3fs_crc_anomaly ABI layout");
@@ -1207,6 +1209,42 @@ int hf3fs_crc_scrub_batch(uint8_t type, hf3fs_crc_scrub_io* d_ios, uint64_t n, u
         return launch_scrub_prep(d_ios, n, type, max_len, addr, len, maxl, s);
       },
       [&](const uint32_t* v) { return launch_scrub_finalize(d_ios, n, v, d_mismatch_count, s); }, "scrub", true);
+}
+
+size_t hf3fs_crc_sync_plan_scratch_bytes(uint64_t n_local, uint64_t n_remote) {
+  if (n_local > kSyncMaxRecords || n_remote > kSyncMaxRecords) return 0;
+  return sync_scratch_bytes(n_local, n_remote);
+}
+
+int hf3fs_crc_sync_plan(hf3fs_crc_sync_meta* d_local, uint64_t n_local, hf3fs_crc_sync_meta* d_remote,
+                        uint64_t n_remote, uint32_t chain_ver, uint32_t flags, uint32_t* d_write, uint32_t* d_remove,
+                        uint32_t* d_info, void* stream) {
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if ((!d_local && n_local) || (!d_remote && n_remote)) return fail(HF3FS_CRC_INVALID_ARG, "null table");
+  if (flags & ~(uint32_t)HF3FS_SYNC_HEAVY) return fail(HF3FS_CRC_INVALID_ARG, "unknown flags %#x", flags);
+  if (n_local > kSyncMaxRecords || n_remote > kSyncMaxRecords)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many records (%llu local, %llu remote)", (unsigned long long)n_local,
+                (unsigned long long)n_remote);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // Empty tables take the same launches (every loop is empty): d_info becomes the empty plan.
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, sync_scratch_bytes(n_local, n_remote), &base)) return rc;
+  SyncScratch ss;
+  sync_scratch_carve(base, n_local, n_remote, &ss);
+  HIP_OR_FAIL(launch_sync_plan(d_local, n_local, d_remote, n_remote, chain_ver, flags, d_write, d_remove, d_info, ss, s));
+  return HF3FS_CRC_OK;
+}
+
+int hf3fs_crc_sync_scrub_fill(const hf3fs_crc_sync_meta* d_local, const uint64_t* d_addrs, const uint32_t* d_write,
+                              const uint32_t* d_info, uint64_t n_local, hf3fs_crc_scrub_io* d_scrub, void* stream) {
+  if (n_local == 0) return HF3FS_CRC_OK;
+  if (!d_local || !d_addrs || !d_write || !d_info || !d_scrub) return fail(HF3FS_CRC_INVALID_ARG, "null argument");
+  if (n_local > kSyncMaxRecords)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many records (%llu)", (unsigned long long)n_local);
+  HIP_OR_FAIL(launch_sync_scrub_fill(d_local, d_addrs, d_write, d_info, n_local, d_scrub, (hipStream_t)stream));
+  return HF3FS_CRC_OK;
 }
 
 int hf3fs_crc_frame_verify_batch(const void* d_buf, hf3fs_crc_frame* d_frames, uint64_t n, uint32_t max_size,

@@ -508,6 +508,115 @@ typedef struct hf3fs_crc_scrub_io {
 int hf3fs_crc_scrub_batch(uint8_t type, hf3fs_crc_scrub_io *d_ios, uint64_t n, uint32_t max_len,
                           uint32_t *d_mismatch_count, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* resync plan: the comparison loop of ResyncWorker::handleSync               */
+/* ------------------------------------------------------------------------ */
+/* One chunk's metadata as the resync comparison reads it (src/storage/sync/ResyncWorker.cc:199-303):
+ * a record of the local table is a ChunkMetadata of getAllMetadataMap, a record of the remote table
+ * a ChunkMeta the successor returned from syncStart.  One layout serves both.  Chunk ids are the 16
+ * bytes of ChunkId(high, low) (Common.cc:10-18); ids of any other length are outside this call. */
+typedef struct hf3fs_crc_sync_meta {
+  uint64_t id_hi, id_lo;    /* ChunkId(high, low) (Common.cc:10-18); equality only */
+  uint32_t chain_ver;       /* ChunkMeta.chainVer / ChunkMetadata.chainVer */
+  uint32_t update_ver, commit_ver;
+  uint32_t checksum;        /* raw value */
+  uint32_t length;          /* ChunkMeta.length / ChunkMetadata.size (carried, not compared) */
+  uint32_t chunk_size;      /* local: innerFileId.chunkSize (the write list's second member); remote: 0 */
+  uint8_t chunk_state;      /* ChunkState: COMMIT 0, DIRTY 1, CLEAN 2 */
+  uint8_t recycle_state;    /* local: RecycleState, 0 = NORMAL; remote: 0 */
+  uint8_t checksum_type;
+  uint8_t out_class;        /* out: HF3FS_SYNC_* below */
+  uint32_t out_peer;        /* out: index of the matched record in the other table, 0xFFFFFFFF if none */
+} hf3fs_crc_sync_meta;
+
+/* out_class of a remote record: the first rung of the ladder (ResyncWorker.cc:203-275) that holds;
+ * "local" is the local record with the same id, chain_ver the call's argument. */
+enum {
+  HF3FS_SYNC_REMOTE_ONLY = 1,             /* no local record, or an earlier remote record with this id took
+                                             it (:205-210): remove at the successor */
+  HF3FS_SYNC_LOCAL_RECYCLING = 2,         /* local.recycle_state != NORMAL (:215-219): nothing */
+  HF3FS_SYNC_CHAIN_VER_LOW = 3,           /* local.chain_ver > remote.chain_ver: forward */
+  HF3FS_SYNC_REMOTE_UNCOMMITTED = 4,      /* remote update_ver != commit_ver or state != COMMIT: forward */
+  HF3FS_SYNC_REMOTE_CHAIN_VER_HIGH = 5,   /* local.chain_ver < remote's, local COMMIT: fatal */
+  HF3FS_SYNC_LOCAL_UNCOMMITTED = 6,       /* the same, local not COMMIT: skip */
+  HF3FS_SYNC_COMMIT_VER_MISMATCH = 7,     /* local.update_ver != remote.commit_ver, local.chain_ver !=
+                                             chain_ver, local COMMIT: fatal */
+  HF3FS_SYNC_CHAIN_WRITING = 8,           /* local.update_ver != remote.commit_ver otherwise: skip */
+  HF3FS_SYNC_FULL_SYNC_HEAVY = 9,         /* flag HF3FS_SYNC_HEAVY: forward */
+  HF3FS_SYNC_CHECKSUM_MISMATCH = 10,      /* {type, value} differ (Common.h:200), local.chain_ver !=
+                                             chain_ver: fatal */
+  HF3FS_SYNC_CHAIN_WRITING_CHECKSUM = 11, /* {type, value} differ otherwise: skip */
+  HF3FS_SYNC_EQUAL = 12,                  /* skip */
+  /* out_class of a local record */
+  HF3FS_SYNC_MATCHED = 16,     /* a remote record took it: out_peer = the lowest-indexed remote record
+                                  with its id (also when the record is recycling) */
+  HF3FS_SYNC_REMOTE_MISS = 17, /* no remote record has its id: forward (:289-292), recycling or not */
+  HF3FS_SYNC_DUPLICATE = 18    /* an earlier local record has the same id (the reference's table is a
+                                  map: it cannot happen there).  Never matched, never forwarded */
+};
+
+/* Words of d_info. */
+enum {
+  HF3FS_SYNC_INFO_FATAL = 0,               /* 0 or 1 (hasFatalEvents) */
+  HF3FS_SYNC_INFO_FIRST_FATAL = 1,         /* lowest remote index with a fatal class, else 0xFFFFFFFF */
+  HF3FS_SYNC_INFO_N_WRITE = 2,
+  HF3FS_SYNC_INFO_N_REMOVE = 3,
+  HF3FS_SYNC_INFO_RECYCLE = 4,             /* storage.syncing.chunk_in_recycle_state */
+  HF3FS_SYNC_INFO_CHAIN_VER_LOW = 5,       /* .chain_version_low */
+  HF3FS_SYNC_INFO_REMOTE_UNCOMMITTED = 6,  /* .remote_uncommitted */
+  HF3FS_SYNC_INFO_CHAIN_VER_HIGH = 7,      /* .chain_version_high */
+  HF3FS_SYNC_INFO_LOCAL_UNCOMMITTED = 8,   /* .local_uncommitted */
+  HF3FS_SYNC_INFO_COMMIT_VER_MISMATCH = 9, /* .commit_version_mismatch */
+  HF3FS_SYNC_INFO_CHAIN_WRITING = 10,      /* .current_chain_is_writing (both of its rungs) */
+  HF3FS_SYNC_INFO_FULL_SYNC_HEAVY = 11,    /* .full_sync_heavy */
+  HF3FS_SYNC_INFO_FULL_SYNC_LIGHT = 12,    /* .full_sync_light */
+  HF3FS_SYNC_INFO_SKIP = 13,               /* .skip_count: LOCAL_UNCOMMITTED, both CHAIN_WRITING classes and
+                                              EQUAL; not LOCAL_RECYCLING (:218 continues before :273), not a
+                                              fatal record */
+  HF3FS_SYNC_INFO_REMOTE_MISS = 14,        /* .remote_miss_count */
+  HF3FS_SYNC_INFO_DUPLICATES = 15,         /* local records of class DUPLICATE (whole table, fatal or not) */
+  HF3FS_SYNC_INFO_WORDS = 16
+};
+enum { HF3FS_SYNC_HEAVY = 1 }; /* flags: FullSyncLevel::HEAVY for this chain (:102-105) */
+
+/* The comparison loop as one stream-ordered call: a hash join of the two tables on the 128-bit id,
+ * then the ladder.  Writes out_class and out_peer of every record of both tables (a record's class
+ * does not depend on the break below) and all HF3FS_SYNC_INFO_WORDS words of d_info.
+ * Break: the reference stops at the first fatal record (:232,243,256) and builds no lists
+ * (:277-287).  So with fatal == 1 the ladder counters (words 4-13) cover the remote records
+ * [0, first_fatal] -- what the reference's local variables hold at the break -- remote_miss, n_write
+ * and n_remove are 0 and the list contents are unspecified.
+ * Lists (fatal == 0): d_write (capacity n_local) receives, ascending, the local indices to forward:
+ * MATCHED records whose peer is CHAIN_VER_LOW, REMOTE_UNCOMMITTED or FULL_SYNC_HEAVY, and
+ * REMOTE_MISS records.  d_remove (capacity n_remote) receives, ascending, the REMOTE_ONLY remote
+ * indices.  The reference's own order is remote order followed by unordered_map order, which is
+ * unspecified, and the forwards are independent of each other: ascending index is this call's.
+ * Either list pointer may be NULL; the counts are set all the same.
+ * Errors, all checked before any device is touched: null d_info, a null table with a non-zero
+ * count, unknown flag bits, n_local or n_remote above 2^30 -> kInvalidArg.  n_local == n_remote
+ * == 0 is OK: d_info is the empty plan.
+ * Stream behaviour follows hf3fs_crc_update_ordered: asynchronous on `stream`, no host
+ * synchronisation, nothing read back; capturable, also as the process's first library call; a
+ * replayed graph re-plans from what the tables hold at replay time.  Scratch per (stream, thread)
+ * pair outside a capture and graph-owned inside one, never the stream-ordered pool; every scratch
+ * word read is written by the call first (option poison). */
+int hf3fs_crc_sync_plan(hf3fs_crc_sync_meta *d_local, uint64_t n_local, hf3fs_crc_sync_meta *d_remote,
+                        uint64_t n_remote, uint32_t chain_ver, uint32_t flags, uint32_t *d_write,
+                        uint32_t *d_remove, uint32_t *d_info, void *stream);
+/* Bytes of scratch one such call takes: after one call of the largest (n_local, n_remote) nothing
+ * grows.  0 for counts the call rejects. */
+size_t hf3fs_crc_sync_plan_scratch_bytes(uint64_t n_local, uint64_t n_remote);
+
+/* Plan -> recheck without a host round trip: turns the plan's write list into n_local scrub
+ * records.  d_addrs[i] is the device address of local chunk i; n_write is read from d_info on the
+ * device.  Record k < n_write describes local record d_write[k]: data, length, checksum_type, raw
+ * checksum, fin 0.  Every other record is {data 0, length 0, type NONE}, which
+ * hf3fs_crc_scrub_batch passes unchecked: the caller runs hf3fs_crc_scrub_batch(type, d_scrub,
+ * n_local, ...) on the same stream.  Null arguments with n_local > 0 -> kInvalidArg; n_local == 0
+ * is OK. */
+int hf3fs_crc_sync_scrub_fill(const hf3fs_crc_sync_meta *d_local, const uint64_t *d_addrs, const uint32_t *d_write,
+                              const uint32_t *d_info, uint64_t n_local, hf3fs_crc_scrub_io *d_scrub, void *stream);
+
 /* The chunk engine's persisted ChunkMeta (chunk_meta.rs:7-20) in its derse
  * wire form: a one-byte body length, then pos u64, chain_ver, chunk_ver, len,
  * checksum (u32 each), timestamp, last_request_id, last_client_low/high (u64
