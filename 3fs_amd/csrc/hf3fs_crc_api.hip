@@ -30,6 +30,7 @@
 #include "order_kernels.h"
 #include "sync_kernels.h"
 #include "update_kernels.h"
+#include "update_plan.h"  // kPlanRanges
 
 static_assert(sizeof(hf3fs_crc_update_io) == 56, "hf3fs_crc_update_io ABI layout");
 static_assert(sizeof(hf3fs_crc_read_io) == 48, "hf3fs_crc_read_io ABI layout");
@@ -840,31 +841,33 @@ size_t hf3fs_crc_update_scratch_bytes(uint64_t n, int mode) {
   bool unfused = false;
   uint32_t pieces = 0, piece_min = 0;
   update_pipeline(mode, &unfused, &pieces, &piece_min);
-  return update_scratch_bytes(n, pieces, (uint32_t)c->cus * kWaves, 0);
+  return update_scratch_bytes(n, update_record_cap(n, 2, pieces), (uint32_t)c->cus * kWaves, 0);
 }
 
-// The apply of a three-pass update call: one-shot (a workgroup per piece of
-// 2^shift destination bytes) on a grid sized from the pair's previous call, or the ticketed
-// tasks when no call has counted pieces yet (option apply_grid) or the piece table would be
-// too large.
-struct ApplyPlan {
+// The plan of one update call: what the options make of it in `mode` -- the pipeline, the
+// ticketed apply's pieces, the waves of its hash launches (pre-hash byte runs: prehash_rep runs
+// per wave, Plan::run_rep) -- and its apply: one-shot (a workgroup per piece of
+// 2^shift destination bytes) on a grid sized from the pair's previous call, or the ticketed tasks
+// when no call has counted pieces yet (option apply_grid) or the piece table would be too large.
+// The entry point is also the index of the pair's hint word: what one entry point counts never
+// sizes the grid of another on the same pair.
+enum UpdateEntry { kEntryBatch = 0, kEntryOrdered = 1, kEntryCow = 2 };  // ordered: its round 0
+struct UpdatePlan {
+  bool unfused = false;
+  uint32_t pieces = 0, piece_min = 0, rep = 1, nw = 0;
+  uint32_t rpi = 2;               // range records per IO: kPlanRanges for a call with destinations
+  const uint64_t* dst = nullptr;  // its destinations (device, may be null)
+  uint64_t records = 0;           // entries of the record array (update_record_cap)
   bool one_shot = false;
   uint32_t shift = 13;
   uint32_t grid = 0;
-  uint64_t ptab_cap = 0;
+  uint64_t cap = 0;       // piece-table entries a one-shot apply of this shape takes, 0: always ticketed
+  uint64_t ptab_cap = 0;  // those of this call (0: it is ticketed)
   uint64_t* hint = nullptr;  // device view of the pair's pinned hint word
-  bool cow = false;          // hf3fs_crc_update_cow_batch: four range records per IO, always one-shot
-  const uint64_t* dst = nullptr;  // its destinations (device, may be null)
 };
 uint32_t apply_piece_shift() {
   const uint32_t kib = options().apply_piece_kib.load();
   return kib <= 4 ? 12 : kib <= 8 ? 13 : 14;
-}
-// Piece-table entries a one-shot apply of this shape would take, 0 where the options or the size
-// rule it out (then every call of the shape is ticketed).
-uint64_t one_shot_cap(uint64_t n, uint32_t max_len) {
-  const uint64_t cap = update_piece_cap(n, max_len, apply_piece_shift());
-  return options().apply_grid.load() == 0 || cap >= (1ull << 31) || cap * 4 > (1ull << 30) ? 0 : cap;
 }
 // The one-shot grid for n IOs from a hint word (pieces << 32 | n of the pair's previous call):
 // that call's pieces per IO with 3 % + 64 workgroups of headroom, at most cap; 0 = no call yet.
@@ -874,28 +877,58 @@ static uint32_t hinted_grid(uint64_t h, uint64_t n, uint64_t cap) {
   const uint64_t want = prev_pieces * n / prev_n;
   return (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, want + want / 32 + 64));
 }
-// which: the pair's hint word -- 0 update_batch's, 1 the one of update_ordered's first round
-// (2 is update_cow_batch's, plan_apply_cow below).
-int plan_apply(Context* c, hipStream_t s, uint64_t n, uint32_t max_len, ApplyPlan* ap, int which = 0) {
-  const Options& o = options();
-  ap->shift = apply_piece_shift();
-  ap->grid = (uint32_t)c->cus * 8;
+// s null: the shape only (what the *_scratch_bytes functions need), no hint is read.
+// hf3fs_crc_update_cow_batch differs in this: it pins the three-pass pipeline with the one-shot
+// apply in both modes -- its range records (payload, gap, old prefix, old suffix: 4 per IO) are
+// the one-shot apply's, and that kernel loops when the grid is short of the piece count, so no
+// call needs the ticketed tasks and the pair's first call takes their grid instead; its piece
+// table has its own bound, and a table over 1 GiB rejects the call where the others fall back
+// to tickets.
+static int plan_update(Context* c, UpdateEntry entry, uint64_t n, uint32_t max_len, int mode, const uint64_t* d_dst,
+                       const hipStream_t* s, UpdatePlan* p) {
+  const bool cow = entry == kEntryCow;
+  const int apply_grid = options().apply_grid.load();
+  update_pipeline(mode, &p->unfused, &p->pieces, &p->piece_min);
+  if (cow) {
+    p->unfused = true;
+    p->pieces = 0;  // no ticketed apply
+  }
+  p->rpi = cow ? kPlanRanges : 2;
+  p->dst = d_dst;
+  p->records = update_record_cap(n, p->rpi, p->pieces);
+  p->rep = std::max<uint32_t>(1, options().prehash_rep.load());
+  p->nw = (uint32_t)c->cus * kWaves * p->rep;
+  if (!p->unfused) return HF3FS_CRC_OK;
+  p->shift = apply_piece_shift();
+  p->grid = (uint32_t)c->cus * 8;  // the ticketed apply's
+  uint64_t cap = cow ? update_cow_piece_cap(n, max_len, p->shift) : update_piece_cap(n, max_len, p->shift);
+  if (cap >= (1ull << 31) || cap * 4 > (1ull << 30) || (cow && n >= (1ull << 28))) cap = 0;
+  if (cow && !cap)
+    return fail(HF3FS_CRC_INVALID_ARG, "piece table of %llu IOs of %u bytes exceeds 1 GiB: split the batch",
+                (unsigned long long)n, max_len);
+  if (!cow && apply_grid == 0) cap = 0;
+  p->cap = cap;
+  if (cow) p->ptab_cap = cap;
+  if (!s) return HF3FS_CRC_OK;
   uint64_t* host = nullptr;
-  if (int rc = c->hint_word(s, which, &host, &ap->hint)) return rc;
-  const int mode = o.apply_grid.load();
-  const uint64_t cap = one_shot_cap(n, max_len);
+  if (int rc = c->hint_word(*s, entry, &host, &p->hint)) return rc;
   if (!cap) return HF3FS_CRC_OK;  // tickets
-  const uint64_t h = __atomic_load_n(host, __ATOMIC_ACQUIRE);
-  const uint32_t hinted = hinted_grid(h, n, cap);
-  if (mode == 2) {  // test: a small grid, every workgroup loops over several pieces
-    ap->grid = (uint32_t)c->cus;
+  const uint32_t hinted = hinted_grid(__atomic_load_n(host, __ATOMIC_ACQUIRE), n, cap);
+  if (apply_grid == 2) {  // test: a small grid, every workgroup loops over several pieces
+    p->grid = (uint32_t)c->cus;
   } else if (hinted) {
-    ap->grid = hinted;
-  } else if (mode < 0) {
+    p->grid = hinted;
+  } else if (!cow && apply_grid < 0) {
     return HF3FS_CRC_OK;  // auto, first call of the pair: tickets (they count the pieces)
   }
-  ap->one_shot = true;
-  ap->ptab_cap = cap;
+  p->one_shot = true;
+  p->ptab_cap = cap;
+  return HF3FS_CRC_OK;
+}
+static int update_args(uint8_t type, int mode) {
+  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
+  if (mode != HF3FS_UPDATE_MODE_REFERENCE && mode != HF3FS_UPDATE_MODE_DELTA)
+    return fail(HF3FS_CRC_INVALID_ARG, "unknown update mode %d", mode);
   return HF3FS_CRC_OK;
 }
 
@@ -916,62 +949,45 @@ struct SideJoin {
   ~SideJoin() { if (forked) (void)wait(); }
 };
 
-// What the options make of an update call in `mode`: the pipeline, its apply pieces and the
-// waves of its hash launches (pre-hash byte runs: prehash_rep runs per wave, Plan::run_rep).
-struct UpdateGeom {
-  bool unfused = false;
-  uint32_t pieces = 0, piece_min = 0, rep = 1, nw = 0;
-};
-static void update_geometry(const Context* c, int mode, UpdateGeom* g) {
-  update_pipeline(mode, &g->unfused, &g->pieces, &g->piece_min);
-  g->rep = std::max<uint32_t>(1, options().prehash_rep.load());
-  g->nw = (uint32_t)c->cus * kWaves * g->rep;
-}
 static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
-                      const UpdateGeom& g, const ApplyPlan& ap, void* base, hipStream_t s);
+                      const UpdatePlan& p, void* base, hipStream_t s);
 
 int hf3fs_crc_update_batch(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
                            void* stream) {
-  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
-  if (mode != HF3FS_UPDATE_MODE_REFERENCE && mode != HF3FS_UPDATE_MODE_DELTA)
-    return fail(HF3FS_CRC_INVALID_ARG, "unknown update mode %d", mode);
+  if (int rc = update_args(type, mode)) return rc;
   if (n == 0) return HF3FS_CRC_OK;
   if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
   Context* c = nullptr;
   if (int rc = get_context(&c)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  UpdateGeom g;
-  update_geometry(c, mode, &g);
-  ApplyPlan ap;
-  if (g.unfused)
-    if (int rc = plan_apply(c, s, n, max_len, &ap)) return rc;
+  UpdatePlan p;
+  if (int rc = plan_update(c, kEntryBatch, n, max_len, mode, nullptr, &s, &p)) return rc;
   void* base = nullptr;
-  if (int rc = call_scratch(c, s, update_scratch_bytes(n, g.pieces, g.nw, ap.ptab_cap), &base)) return rc;
-  return update_run(c, type, d_ios, n, max_len, mode, g, ap, base, s);
+  if (int rc = call_scratch(c, s, update_scratch_bytes(n, p.records, p.nw, p.ptab_cap), &base)) return rc;
+  return update_run(c, type, d_ios, n, max_len, mode, p, base, s);
 }
 
 // One pass of the update pipeline over n IOs on DISTINCT chunks, on scratch the caller got for it
-// (update_scratch_bytes(n, g.pieces, g.nw, ap.ptab_cap) at base): hf3fs_crc_update_batch, and every
-// round of hf3fs_crc_update_ordered.
+// (update_scratch_bytes(n, p.records, p.nw, p.ptab_cap) at base): hf3fs_crc_update_batch,
+// hf3fs_crc_update_cow_batch, and every round of hf3fs_crc_update_ordered.
 static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
-                      const UpdateGeom& g, const ApplyPlan& ap, void* base, hipStream_t s) {
+                      const UpdatePlan& p, void* base, hipStream_t s) {
   const uint8_t ktype = type == kTypeNone ? kTypeCrc32c : type;
-  const bool unfused = g.unfused;
-  const uint32_t pieces = g.pieces, piece_min = g.piece_min, rep = g.rep, nw = g.nw;
+  const bool unfused = p.unfused;
   // Pre-hash task size: 512 KiB segments of the payload / old-byte jobs (A/B on d3 DELTA:
   // 1.766-1.772 ms per batch vs 1.788-1.797 at 256 KiB, 1.85 at 1 MiB; gpurun_out r03 seg sweep).
   constexpr uint64_t kPreSeg = 512 << 10;
   UpdateScratch sc;
-  update_scratch_carve(base, n, pieces, piece_min, nw, ap.ptab_cap, &sc);
-  sc.piece_shift = ap.shift;
-  sc.one_shot = ap.one_shot ? 1u : 0u;
+  update_scratch_carve(base, n, p.records, p.pieces, p.piece_min, p.nw, p.ptab_cap, &sc);
+  sc.piece_shift = p.shift;
+  sc.one_shot = p.one_shot ? 1u : 0u;
   sc.diag = c->diag;
   sc.runs_used = unfused;
   sc.fault_io = options().fault_io.load();
   // Pre hash as byte runs: every wave the same share of payload + old bytes, ranges split
   // anywhere (A/B vs 512 KiB tickets: 1.721-1.732 vs 1.726-1.738 ms per d3 DELTA batch).
   const bool prep_runs = 2 * n <= kPrepRunJobs;  // prep's runs workgroup places them (else launch_balance)
-  const ByteRuns runs{sc.run_partial, sc.run_bal, sc.run_boff, sc.run_blocks, prep_runs, rep};
+  const ByteRuns runs{sc.run_partial, sc.run_bal, sc.run_boff, sc.run_blocks, prep_runs, p.rep};
   // ONE zeroing launch: the job maxima, the task count and every ticket counter of this
   // call live in sc.ctl; prep zeroes the per-IO hash outputs itself.
   HIP_OR_FAIL(launch_zero_words(sc.ctl, kCtlWords, s));
@@ -981,15 +997,12 @@ static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint
     const int nt = (int)options().apply_nt.load();
     HIP_OR_FAIL(launch_update_fused(d_ios, n, max_len, type, mode, sc, c->tables, grid, nt, s));
   } else {  // three passes: prep, the pre jobs through k_crc_ranges, apply (+ finalize of most IOs)
-    if (ap.cow)
-      HIP_OR_FAIL(launch_update_prep_cow(d_ios, ap.dst, n, max_len, type, mode, sc, prep_runs, s));
-    else
-      HIP_OR_FAIL(launch_update_prep(d_ios, n, max_len, type, mode, sc, prep_runs, s));
+    HIP_OR_FAIL(launch_update_prep(d_ios, p.dst, n, max_len, type, mode, sc, p.rpi, prep_runs, s));
     ListSource pre{sc.pre_addr, sc.pre_len, sc.pre_start, 2 * n, 0u};
     if (int rc = run_ranges_list(c, ktype, pre, max_len, sc.pre_out, s, kPreSeg, sc.ctl + kCtlPreMax, nullptr,
                                  sc.ctl + kCtlQueuePre, &runs))
       return rc;
-    if (ap.one_shot) {  // every verdict and every IO without a post job, beside the apply
+    if (p.one_shot) {  // every verdict and every IO without a post job, beside the apply
       if (int rc = c->side_of(s, &join.side)) return rc;
       join.s = s;
       HIP_OR_FAIL(hipEventRecord(join.side.fork, s));
@@ -998,11 +1011,8 @@ static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint
       HIP_OR_FAIL(launch_update_finalize(d_ios, n, type, mode, sc, c->tables, max_len, 1, false, join.side.side));
       HIP_OR_FAIL(join.record());
     }
-    if (ap.cow)
-      HIP_OR_FAIL(launch_update_apply_cow(n, sc, ap.grid, (int)options().apply_nt.load(), ap.ptab_cap, ap.hint, s));
-    else
-      HIP_OR_FAIL(launch_update_apply(d_ios, n, max_len, type, mode, sc, c->tables, true, ap.grid,
-                                      (int)options().apply_nt.load(), ap.ptab_cap, ap.hint, s));
+    HIP_OR_FAIL(launch_update_apply(d_ios, n, max_len, type, mode, sc, c->tables, p.rpi, true, p.grid,
+                                    (int)options().apply_nt.load(), p.ptab_cap, p.hint, s));
   }
   ListSource post{sc.post_addr, sc.post_len, sc.post_start, 2 * n, 0u};
   if (int rc = run_ranges_list(c, ktype, post, max_len, sc.post_out, s, 256 << 10, sc.ctl + kCtlPostMax, nullptr,
@@ -1011,7 +1021,7 @@ static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint
   // the last launch also re-checks every payload it reports as mismatched (option audit)
   // the three-pass pipeline's verdicts came from the apply (ticketed) or the side stream
   // (one-shot): only the post-job IOs and the audit are left
-  if (ap.one_shot) HIP_OR_FAIL(join.wait());
+  if (p.one_shot) HIP_OR_FAIL(join.wait());
   HIP_OR_FAIL(launch_update_finalize(d_ios, n, type, mode, sc, c->tables, max_len, unfused ? 2 : 0,
                                      options().audit.load() != 0, s));
   if (options().debug.load()) {  // diagnostics: job maxima and the first pre/post hashes
@@ -1034,14 +1044,11 @@ static int update_run(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint
 // of a one-shot apply whenever the options allow one, whether or not this call's first round
 // takes it (the pair's hint decides that from call to call, and no later call may need more than
 // the first of a shape got) -- and the planner's arrays behind it.
-static size_t ordered_pipeline_bytes(const UpdateGeom& g, uint64_t n, uint32_t max_len) {
-  const size_t b = update_scratch_bytes(n, g.pieces, g.nw, g.unfused ? one_shot_cap(n, max_len) : 0);
-  return (b + 63) & ~size_t(63);
+static size_t ordered_pipeline_bytes(const UpdatePlan& p, uint64_t n) {
+  return (update_scratch_bytes(n, p.records, p.nw, p.cap) + 63) & ~size_t(63);
 }
 static int ordered_args(uint8_t type, int mode, uint32_t max_rounds) {
-  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
-  if (mode != HF3FS_UPDATE_MODE_REFERENCE && mode != HF3FS_UPDATE_MODE_DELTA)
-    return fail(HF3FS_CRC_INVALID_ARG, "unknown update mode %d", mode);
+  if (int rc = update_args(type, mode)) return rc;
   if (max_rounds < 1 || max_rounds > 64)
     return fail(HF3FS_CRC_INVALID_ARG, "max_rounds %u is not in 1..64", max_rounds);
   return HF3FS_CRC_OK;
@@ -1052,9 +1059,9 @@ size_t hf3fs_crc_update_ordered_scratch_bytes(uint64_t n, uint32_t max_len, int 
   if (ordered_args(kTypeCrc32c, mode, max_rounds) || n == 0 || n > kOrderedMaxIos) return 0;
   Context* c = nullptr;
   if (get_context(&c)) return 0;
-  UpdateGeom g;
-  update_geometry(c, mode, &g);
-  return ordered_pipeline_bytes(g, n, max_len) + order_scratch_bytes(n);
+  UpdatePlan p;
+  if (plan_update(c, kEntryOrdered, n, max_len, mode, nullptr, nullptr, &p)) return 0;
+  return ordered_pipeline_bytes(p, n) + order_scratch_bytes(n);
 }
 
 int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
@@ -1069,19 +1076,18 @@ int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t 
   if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
   Context* c = nullptr;
   if (int rc = get_context(&c)) return rc;
-  UpdateGeom g;
-  update_geometry(c, mode, &g);
   // Round 0 is planned like an update_batch of the n records (with every chunk distinct it IS that
   // call), on a hint word of its own: what an ordered call counts never sizes the grid of a plain
   // update_batch on the same pair.  Later rounds shrink fast and are padded to n records, so a
   // pieces-per-IO figure says nothing about them: they take the ticketed apply, which needs none.
-  ApplyPlan first, later;
-  if (g.unfused) {
-    if (int rc = plan_apply(c, s, n, max_len, &first, 1)) return rc;
-    later.shift = first.shift;
-    later.grid = (uint32_t)c->cus * 8;
-  }
-  const size_t pipe_bytes = ordered_pipeline_bytes(g, n, max_len);
+  UpdatePlan first;
+  if (int rc = plan_update(c, kEntryOrdered, n, max_len, mode, nullptr, &s, &first)) return rc;
+  UpdatePlan later = first;
+  later.one_shot = false;
+  later.ptab_cap = 0;
+  later.hint = nullptr;
+  later.grid = (uint32_t)c->cus * 8;
+  const size_t pipe_bytes = ordered_pipeline_bytes(first, n);
   void* base = nullptr;
   if (int rc = call_scratch(c, s, pipe_bytes + order_scratch_bytes(n), &base)) return rc;
   OrderScratch os;
@@ -1089,80 +1095,34 @@ int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t 
   HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
   for (uint32_t r = 0; r < max_rounds; ++r) {
     HIP_OR_FAIL(launch_order_step(d_ios, n, r, max_rounds, os, nullptr, s));
-    if (int rc = update_run(c, type, os.round, n, max_len, mode, g, r ? later : first, base, s)) return rc;
+    if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
   }
   HIP_OR_FAIL(launch_order_step(d_ios, n, max_rounds, max_rounds, os, d_info, s));
   return HF3FS_CRC_OK;
 }
 
-// hf3fs_crc_update_cow_batch pins the three-pass pipeline with the one-shot apply in both modes:
-// its range records (payload, gap, old prefix, old suffix) are the one-shot apply's, and that
-// kernel loops when the grid is short of the piece count, so no call needs the ticketed tasks.
-static void cow_geometry(const Context* c, UpdateGeom* g) {
-  g->unfused = true;
-  g->pieces = 1;  // update_scratch_bytes / _carve: 2 n (pieces + 1) = 4 n range records
-  g->piece_min = 64 << 10;
-  g->rep = std::max<uint32_t>(1, options().prehash_rep.load());
-  g->nw = (uint32_t)c->cus * kWaves * g->rep;
-}
-// Piece-table entries of the call, 0 when the table would not fit (the call is rejected).
-static uint64_t cow_cap(uint64_t n, uint32_t max_len) {
-  if (n >= (1ull << 28)) return 0;
-  const uint64_t cap = update_cow_piece_cap(n, max_len, apply_piece_shift());
-  return cap >= (1ull << 31) || cap * 4 > (1ull << 30) ? 0 : cap;
-}
-static int cow_args(uint8_t type, int mode) {
-  if (!valid_type(type)) return fail(HF3FS_CRC_INVALID_ARG, "unknown checksum type %u", type);
-  if (mode != HF3FS_UPDATE_MODE_REFERENCE && mode != HF3FS_UPDATE_MODE_DELTA)
-    return fail(HF3FS_CRC_INVALID_ARG, "unknown update mode %d", mode);
-  return HF3FS_CRC_OK;
-}
-
 size_t hf3fs_crc_update_cow_scratch_bytes(uint64_t n, uint32_t max_len, int mode) {
-  if (cow_args(kTypeCrc32c, mode) || n == 0) return 0;
-  const uint64_t cap = cow_cap(n, max_len);
-  if (!cap) return 0;
+  if (update_args(kTypeCrc32c, mode) || n == 0) return 0;
   Context* c = nullptr;
   if (get_context(&c)) return 0;
-  UpdateGeom g;
-  cow_geometry(c, &g);
-  return update_scratch_bytes(n, g.pieces, g.nw, cap);
-}
-
-// The apply of a COW call: always one-shot.  The grid: the pieces per IO of the pair's previous
-// COW call (a hint word of its own: what this call counts never sizes a plain update_batch), the
-// ticketed apply's grid before any call has counted (the one-shot kernel loops over the rest), one
-// workgroup per CU with apply_grid = 2.  ap->ptab_cap is set by the caller.
-static int plan_apply_cow(Context* c, hipStream_t s, uint64_t n, ApplyPlan* ap) {
-  ap->cow = ap->one_shot = true;
-  ap->shift = apply_piece_shift();
-  uint64_t* host = nullptr;
-  if (int rc = c->hint_word(s, 2, &host, &ap->hint)) return rc;
-  const uint32_t hinted = hinted_grid(__atomic_load_n(host, __ATOMIC_ACQUIRE), n, ap->ptab_cap);
-  ap->grid = options().apply_grid.load() == 2 ? (uint32_t)c->cus : hinted ? hinted : (uint32_t)c->cus * 8;
-  return HF3FS_CRC_OK;
+  UpdatePlan p;
+  if (plan_update(c, kEntryCow, n, max_len, mode, nullptr, nullptr, &p)) return 0;
+  return update_scratch_bytes(n, p.records, p.nw, p.ptab_cap);
 }
 
 int hf3fs_crc_update_cow_batch(uint8_t type, hf3fs_crc_update_io* d_ios, const uint64_t* d_dst, uint64_t n,
                                uint32_t max_len, int mode, void* stream) {
-  if (int rc = cow_args(type, mode)) return rc;
+  if (int rc = update_args(type, mode)) return rc;
   if (n == 0) return HF3FS_CRC_OK;
   if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
-  ApplyPlan ap;
-  ap.dst = d_dst;
-  ap.ptab_cap = cow_cap(n, max_len);
-  if (!ap.ptab_cap)
-    return fail(HF3FS_CRC_INVALID_ARG, "piece table of %llu IOs of %u bytes exceeds 1 GiB: split the batch",
-                (unsigned long long)n, max_len);
   Context* c = nullptr;
   if (int rc = get_context(&c)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  UpdateGeom g;
-  cow_geometry(c, &g);
-  if (int rc = plan_apply_cow(c, s, n, &ap)) return rc;
+  UpdatePlan p;
+  if (int rc = plan_update(c, kEntryCow, n, max_len, mode, d_dst, &s, &p)) return rc;
   void* base = nullptr;
-  if (int rc = call_scratch(c, s, update_scratch_bytes(n, g.pieces, g.nw, ap.ptab_cap), &base)) return rc;
-  return update_run(c, type, d_ios, n, max_len, mode, g, ap, base, s);
+  if (int rc = call_scratch(c, s, update_scratch_bytes(n, p.records, p.nw, p.ptab_cap), &base)) return rc;
+  return update_run(c, type, d_ios, n, max_len, mode, p, base, s);
 }
 
 int hf3fs_crc_pair_scratch_stats(void* stream, uint64_t* call_bytes, uint64_t* allocations) {

@@ -57,7 +57,8 @@ struct UpdateScratch {
   // addresses; one workgroup copies one piece and exits.  tasks[2 i] / tasks[2 i + 1] are IO
   // i's payload / gap range records (verify = first piece | verify << 31), ptab[p] the
   // record of piece p.  one_shot = 0: the ticketed tasks above.  With destinations
-  // (k_update_prep_cow) IO i has four records, tasks[4 i + k], k as in update_plan.h plan_ranges.
+  // (k_update_prep<kPlanRanges>) IO i has four records, tasks[4 i + k], k as in update_plan.h
+  // plan_ranges.
   uint32_t* ptab;
   uint32_t piece_shift;
   uint32_t one_shot;
@@ -74,11 +75,15 @@ struct UpdateScratch {
 };
 constexpr uint32_t kRunBlocksMax = 64;  // k_bal_sums blocks for the byte runs of 2n pre jobs
 
+// Entries of the record array (UpdateScratch::tasks) a call of n IOs needs: rpi range records per
+// IO, or where the ticketed apply may run its 2 (pieces + 1) tasks per IO (pieces = 0: it cannot).
+uint64_t update_record_cap(uint64_t n, uint32_t rpi, uint32_t pieces);
+// records: update_record_cap of the call
 // nw: waves of the hash launches (byte-run boundaries)
 // ptab_cap: piece-table entries (one-shot apply), 0 for the ticketed apply
-size_t update_scratch_bytes(uint64_t n, uint32_t pieces, uint32_t nw, uint64_t ptab_cap);
-void update_scratch_carve(void* base, uint64_t n, uint32_t pieces, uint32_t piece_min, uint32_t nw,
-                          uint64_t ptab_cap, UpdateScratch* s);
+size_t update_scratch_bytes(uint64_t n, uint64_t records, uint32_t nw, uint64_t ptab_cap);
+void update_scratch_carve(void* base, uint64_t n, uint64_t records, uint32_t pieces, uint32_t piece_min,
+                          uint32_t nw, uint64_t ptab_cap, UpdateScratch* s);
 // Piece-table entries a batch of n IOs of at most max_len bytes can need (payload + gap).
 uint64_t update_piece_cap(uint64_t n, uint32_t max_len, uint32_t piece_shift);
 // The same for a batch with destinations (hf3fs_crc_update_cow_batch): payload, gap, old prefix
@@ -88,20 +93,17 @@ uint64_t update_cow_piece_cap(uint64_t n, uint32_t max_len, uint32_t piece_shift
 // prep for every IO; with place_runs (2n <= kPrepRunJobs) one extra workgroup places the
 // byte runs of the 2n pre jobs over s.run_waves waves meanwhile (s.run_bal / s.run_boff,
 // launch_balance's boff form).
+// rpi: range records per IO, the same in launch_update_apply.  2: every image in place (dsts is
+// not read), payload and gap records or, with s.one_shot = 0, the ticketed tasks.  kPlanRanges
+// (hf3fs_crc_update_cow_batch; s.one_shot = 1 only): IO i's new image is written at dsts[i]
+// unless that is 0 or the IO's chunk (dsts may be null); prep emits the payload and gap records
+// there plus, out of place, the old prefix and old suffix copied from the chunk.
 constexpr uint32_t kPrepRunJobs = 8192;  // pre jobs the runs workgroup places (8 per thread, in registers)
 constexpr uint32_t kPrepThreads = 1024;  // prep workgroup size (the runs workgroup's)
 constexpr uint32_t kPrepIoThreads = 256;  // threads per prep workgroup deriving IOs
-hipError_t launch_update_prep(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max_len, uint8_t type, int mode,
-                              const UpdateScratch& s, bool place_runs, hipStream_t st);
-// hf3fs_crc_update_cow_batch's prep and apply (one-shot only; s.one_shot = 1, s.tasks holds 4 n
-// range records: update_scratch_bytes / _carve with pieces = 1).  IO i's new image is written at
-// dsts[i] unless that is 0 or the IO's chunk (dsts may be null): prep emits the payload and gap
-// records there plus, out of place, the old prefix and old suffix copied from the chunk; the
-// apply is k_update_apply_one_shot over those records (grid, ptab_cap, hint as below).
-hipError_t launch_update_prep_cow(hf3fs_crc_update_io* ios, const uint64_t* dsts, uint64_t n, uint32_t max_len,
-                                  uint8_t type, int mode, const UpdateScratch& s, bool place_runs, hipStream_t st);
-hipError_t launch_update_apply_cow(uint64_t n, const UpdateScratch& s, uint32_t grid, int nt, uint64_t ptab_cap,
-                                   uint64_t* hint, hipStream_t st);
+hipError_t launch_update_prep(hf3fs_crc_update_io* ios, const uint64_t* dsts, uint64_t n, uint32_t max_len,
+                              uint8_t type, int mode, const UpdateScratch& s, uint32_t rpi, bool place_runs,
+                              hipStream_t st);
 // Copies the verified payloads and zero-fills gaps (apply tasks).  With
 // finalize_delta, the apply workgroups also give every IO its payload verdict
 // (ChunkReplica.cc:193-207) and finalize every IO that needs no post job
@@ -111,10 +113,11 @@ hipError_t launch_update_apply_cow(uint64_t n, const UpdateScratch& s, uint32_t 
 // call's one-shot grid.  With s.one_shot the grid is one workgroup per piece as far as it
 // reaches (more pieces than workgroups: each takes every grid-th piece), and the apply
 // finalizes no IO (finalize_delta is ignored: launch_update_finalize with post_only = false);
-// ptab_cap: the piece table's capacity (entries), >= grid.
+// ptab_cap: the piece table's capacity (entries), >= grid.  The one-shot apply runs over rpi
+// records per IO; the ticketed apply exists for rpi = 2 only.
 hipError_t launch_update_apply(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max_len, uint8_t type, int mode,
-                               const UpdateScratch& s, const DeviceTables* tabs, bool finalize_delta, uint32_t grid,
-                               int nt, uint64_t ptab_cap, uint64_t* hint, hipStream_t st);
+                               const UpdateScratch& s, const DeviceTables* tabs, uint32_t rpi, bool finalize_delta,
+                               uint32_t grid, int nt, uint64_t ptab_cap, uint64_t* hint, hipStream_t st);
 // Fused prep + payload verify + write (+ delta old-byte hash), one workgroup
 // per IO; leaves the scratch as prep -> ranges(pre) -> apply would.
 hipError_t launch_update_fused(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max_len, uint8_t type, int mode,

@@ -91,34 +91,18 @@ __device__ __forceinline__ uint8_t ck_case(const hf3fs_crc_update_io& io, const 
   return (uint64_t)io.offset + io.length > s0 ? HF3FS_CKCASE_COMBINE : HF3FS_CKCASE_NONE;  // safe_write appends
 }
 
-// Lengths of IO i's two pre jobs: the payload (verify) and, for the delta method, the old
-// bytes under the write or the truncated tail.  Only the IO's input fields and Eff.
-__device__ __forceinline__ void pre_lens(const Eff& e, uint64_t& l0, uint64_t& l1) {
-  l0 = l1 = 0;
-  if (!e.ok) return;
-  if (e.hash_payload) l0 = e.len;
-  if (e.kase == 4 && e.delta) {
-    if (!e.te && e.off < e.s0)
-      l1 = (e.off + e.len < e.s0 ? e.off + e.len : e.s0) - e.off;
-    else if (e.te && e.s1 < e.s0)
-      l1 = e.s0 - e.s1;
-  }
-}
-
-// k_update_prep for one IO: status and output defaults, the "pre" jobs
-// (payload; old bytes for the delta method) and the "post" jobs (prefix +
-// suffix after the write, reference algorithm).  Returns the derived IO and the
-// longest pre / post job in pre_max / post_max (the caller raises ctl's maxima).
-// COW (hf3fs_crc_update_cow_batch): the IO's new image is written at `image`, not at io.chunk.
-// The pre jobs still read io.chunk (DELTA's old bytes are the committed version's); the post
-// jobs read the new image, where the prefix holds the zero-filled gap of a write past the size.
-template <bool COW = false>
+// k_update_prep for one IO: status and output defaults, and the hash jobs as update_plan.h
+// plan_jobs states them -- "pre" (payload; old bytes for the delta method) and "post" (prefix +
+// suffix after the write, reference algorithm).  Returns the derived IO and the longest pre /
+// post job in pre_max / post_max (the caller raises ctl's maxima).
+// dst (hf3fs_crc_update_cow_batch's d_dst[i], 0 = in place): the IO's new image is written at
+// plan_image(io.chunk, dst).  The pre jobs still read io.chunk (DELTA's old bytes are the
+// committed version's); the post jobs read the new image.
 __device__ __forceinline__ Eff prep_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i, uint32_t max_len,
                                         uint8_t type, int mode, const UpdateScratch& s, uint32_t& pre_max,
-                                        uint32_t& post_max, uint64_t image = 0) {
+                                        uint32_t& post_max, uint64_t dst = 0) {
   const hf3fs_crc_update_io io = ios[i];
   const Eff e = derive(io, max_len, type, mode);
-  const uint64_t written = COW ? image : io.chunk;
   // only the output fields are stored: the prep launch's runs workgroup reads the input
   // fields of the same records meanwhile (bal_runs_block), so they are never rewritten
   ios[i].status = e.ok ? HF3FS_CRC_OK : HF3FS_CRC_INVALID_ARG;
@@ -126,59 +110,27 @@ __device__ __forceinline__ Eff prep_one(hf3fs_crc_update_io* __restrict__ ios, u
   ios[i].out_checksum = io.chunk_checksum;
   ios[i].out_checksum_type = io.chunk_checksum_type;
   ios[i].checksum_case = 0;
-  uint64_t a0 = 0, l0 = 0, a1 = 0, l1 = 0, pa = 0, pl = 0, sa = 0, sl = 0;
-  pre_lens(e, l0, l1);
-  if (l0) a0 = io.payload;
-  if (l1) a1 = io.chunk + (e.te ? e.s1 : e.off);  // old bytes under the write, or the truncated tail
-  if (e.ok) {
-    if (e.kase == 4 && !e.delta) {  // reference: prefix + suffix after the write
-      const uint32_t suffix_start = e.off + e.len < e.s1 ? e.off + e.len : e.s1;
-      pa = written;
-      pl = e.off;
-      sa = written + suffix_start;
-      sl = e.s1 - suffix_start;
-    }
-  }
-  s.pre_addr[2 * i] = a0;
-  s.pre_len[2 * i] = l0;
+  const PlanJobs J = plan_jobs(io, e, plan_image(io.chunk, dst));
+  const PlanJob &p0 = J.job[kJobPayload], &p1 = J.job[kJobOld], &q0 = J.job[kJobPrefix], &q1 = J.job[kJobSuffix];
+  s.pre_addr[2 * i] = p0.addr;
+  s.pre_len[2 * i] = p0.len;
   s.pre_start[2 * i] = ~0u ^ (s.fault_io == i + 1 ? 1u : 0u);
-  s.pre_addr[2 * i + 1] = a1;
-  s.pre_len[2 * i + 1] = l1;
+  s.pre_addr[2 * i + 1] = p1.addr;
+  s.pre_len[2 * i + 1] = p1.len;
   s.pre_start[2 * i + 1] = 0u;
-  s.post_addr[2 * i] = pa;
-  s.post_len[2 * i] = pl;
+  s.post_addr[2 * i] = q0.addr;
+  s.post_len[2 * i] = q0.len;
   s.post_start[2 * i] = ~0u;
-  s.post_addr[2 * i + 1] = sa;
-  s.post_len[2 * i + 1] = sl;
+  s.post_addr[2 * i + 1] = q1.addr;
+  s.post_len[2 * i + 1] = q1.len;
   s.post_start[2 * i + 1] = ~0u;
   s.pre_out[2 * i] = 0u;  // the range hashes XOR segment values into these
   s.pre_out[2 * i + 1] = 0u;
   s.post_out[2 * i] = 0u;
   s.post_out[2 * i + 1] = 0u;
-  pre_max = (uint32_t)(l0 > l1 ? l0 : l1);
-  post_max = (uint32_t)(pl > sl ? pl : sl);
+  pre_max = (uint32_t)(p0.len > p1.len ? p0.len : p1.len);
+  post_max = (uint32_t)(q0.len > q1.len ? q0.len : q1.len);
   return e;
-}
-
-// Apply pieces of a range of len bytes at dst: cuts at 16-byte aligned
-// destination addresses, piece j = [max(0, j ps - h), min(len, (j + 1) ps - h)).
-__device__ __forceinline__ uint64_t piece_bytes(uint64_t len, const UpdateScratch& s) {
-  const uint64_t even = ((len + s.pieces - 1) / s.pieces + 15) & ~uint64_t(15);
-  return even > s.piece_min ? even : s.piece_min;
-}
-__device__ __forceinline__ uint32_t piece_count(uint64_t dst, uint64_t len, const UpdateScratch& s) {
-  if (!len) return 0;
-  const uint64_t ps = piece_bytes(len, s);
-  return (uint32_t)(((dst & 15) + len + ps - 1) / ps);
-}
-
-// Piece j of a range of len bytes at dst (j < piece_count).
-__device__ __forceinline__ void piece_bounds(uint64_t dst, uint64_t len, uint32_t j, const UpdateScratch& s,
-                                             uint64_t& a, uint64_t& b) {
-  const uint64_t ps = piece_bytes(len, s), h = dst & 15;
-  a = j ? (uint64_t)j * ps - h : 0;
-  const uint64_t b0 = (uint64_t)(j + 1) * ps - h;
-  b = b0 < len ? b0 : len;
 }
 
 // Byte runs of the 2n pre jobs over nw waves, by ONE extra workgroup of the prep launch
@@ -192,7 +144,7 @@ __device__ __forceinline__ void piece_bounds(uint64_t dst, uint64_t len, uint32_
 // wave scan and one LDS step over the wave totals give every thread its byte prefix.
 constexpr uint32_t kRunIos = kPrepRunJobs / 2 / kPrepThreads;
 static_assert(kRunIos * 2 * kPrepThreads == kPrepRunJobs, "runs workgroup geometry");
-// (forced inline: both prep kernels run it, and called out of line its uniform arguments would
+// (forced inline: both k_update_prep instantiations run it, and called out of line its uniform arguments would
 // travel in vector registers)
 __device__ __forceinline__ void bal_runs_block(const hf3fs_crc_update_io* __restrict__ ios, uint32_t n, uint32_t max_len,
                                uint8_t type, int mode, uint32_t nw, uint32_t* __restrict__ bal,
@@ -273,16 +225,23 @@ __device__ __forceinline__ void bal_runs_block(const hf3fs_crc_update_io* __rest
   }
 }
 
-// prep for every IO (one thread each) and the compacted apply task list:
-// each wave scans its lanes' piece counts and reserves their slots with one
-// atomic.  The loop bound is wave-uniform (blockDim is a multiple of 64).  With
-// place_runs one extra workgroup places the pre hash's byte runs meanwhile
-// (bal_runs_block): no balance launches between prep and the hash.
-__global__ __launch_bounds__(kPrepThreads) void k_update_prep(hf3fs_crc_update_io* __restrict__ ios, uint64_t n,
-                                                     uint32_t max_len, uint8_t type, int mode, UpdateScratch s,
-                                                     int place_runs) {
+// prep for every IO (one thread each) and what the apply runs on.  RPI is the range records per
+// IO: 2 in place (update_plan.h plan_ranges with image == chunk: payload, gap), kPlanRanges with
+// destinations (hf3fs_crc_update_cow_batch: IO i's image at plan_image(chunk, dsts[i]), plus the
+// old prefix and old suffix; dsts may be null, every IO in place).  One-shot apply: the records at
+// tasks[RPI i + k] -- every one carries the IO's verify bit, a failed payload verify copies no old
+// byte either -- and ptab[p] the record of piece p, an IO's pieces in record order.  Ticketed
+// apply (RPI = 2 only, s.one_shot = 0): the compacted task list.  Either way each wave scans its
+// lanes' counts and reserves their slots with one atomic.  The loop bound is wave-uniform
+// (blockDim is a multiple of 64).  With place_runs one extra workgroup places the pre hash's byte
+// runs meanwhile (bal_runs_block): no balance launches between prep and the hash.
+template <uint32_t RPI>
+__global__ __launch_bounds__(kPrepThreads) void k_update_prep(hf3fs_crc_update_io* __restrict__ ios,
+                                                              const uint64_t* __restrict__ dsts, uint64_t n,
+                                                              uint32_t max_len, uint8_t type, int mode,
+                                                              UpdateScratch s, int place_runs) {
+  static_assert(RPI == 2 || RPI == kPlanRanges, "records per IO");
   const uint32_t lane = threadIdx.x & 63;
-  unsigned long long* count = reinterpret_cast<unsigned long long*>(s.ctl + kCtlTasks);
   unsigned long long* pieces = reinterpret_cast<unsigned long long*>(s.ctl + kCtlPieces);
   // the IOs go to the first kPrepIoThreads threads of each workgroup (4 waves): a launch of
   // n / 256 workgroups spreads the per-IO latency chains over 4x the CUs that 1024 IOs per
@@ -290,33 +249,33 @@ __global__ __launch_bounds__(kPrepThreads) void k_update_prep(hf3fs_crc_update_i
   for (uint64_t i0 = (uint64_t)blockIdx.x * kPrepIoThreads + (threadIdx.x & ~63u);
        threadIdx.x < kPrepIoThreads && i0 < n; i0 += (uint64_t)gridDim.x * kPrepIoThreads) {
     const uint64_t i = i0 + lane;
-    uint32_t np = 0, ng = 0;
-    uint64_t pdst = 0, plen = 0, psrc = 0, gdst = 0, glen = 0;
+    PlanRange R[kPlanRanges] = {};
     uint32_t wval = 0, verify = 0, pre_max = 0, post_max = 0;
     if (i < n) {
-      const Eff e = prep_one(ios, i, max_len, type, mode, s, pre_max, post_max);
+      const hf3fs_crc_update_io io = ios[i];
+      const uint64_t dst = RPI == 2 || !dsts ? 0 : dsts[i];
+      const Eff e = prep_one(ios, i, max_len, type, mode, s, pre_max, post_max, dst);
+      plan_ranges(io, e, plan_image(io.chunk, dst), R);
       if (e.ok) {
-        const uint64_t chunk = ios[i].chunk;
-        if (!e.te) {
-          pdst = chunk + e.off;
-          plen = e.len;
-          psrc = ios[i].payload;
-          np = piece_count(pdst, plen, s);
-        }
-        if (e.zero_to > e.zero_from) {
-          gdst = chunk + e.zero_from;
-          glen = e.zero_to - e.zero_from;
-          ng = piece_count(gdst, glen, s);
-        }
         wval = e.wval;
         verify = e.verify;
       }
     }
-    // one-shot pieces of the payload and the gap (the one-shot apply's table; in ticket mode
-    // only counted, for the next call's grid)
-    const uint32_t pp = pieces_of(pdst, plen, s.piece_shift), pg = pieces_of(gdst, glen, s.piece_shift);
-    const uint32_t k = s.one_shot ? pp + pg : np + ng;
-    uint32_t incl = k, pinc = pp + pg;
+    uint32_t before[RPI + 1];  // one-shot pieces of the IO's earlier ranges
+    before[0] = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < RPI; ++k) before[k + 1] = before[k] + pieces_of(R[k].dst, R[k].len, s.piece_shift);
+    // the slots the IO reserves: its one-shot pieces (the piece table), or its ticketed tasks --
+    // the one-shot pieces are then only counted, for the next call's grid
+    uint32_t cnt_io = before[RPI], pinc = before[RPI], tk[2] = {0, 0};
+    if constexpr (RPI == 2) {
+      if (!s.one_shot) {
+        tk[0] = piece_count(R[0].dst, R[0].len, s.pieces, s.piece_min);
+        tk[1] = piece_count(R[1].dst, R[1].len, s.pieces, s.piece_min);
+        cnt_io = tk[0] + tk[1];
+      }
+    }
+    uint32_t incl = cnt_io;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
       const uint32_t y = __shfl_up(incl, d);
@@ -324,114 +283,62 @@ __global__ __launch_bounds__(kPrepThreads) void k_update_prep(hf3fs_crc_update_i
       // the wave's job maxima: one atomic per wave, not one per IO on the same word
       pre_max = max(pre_max, (uint32_t)__shfl_xor(pre_max, d));
       post_max = max(post_max, (uint32_t)__shfl_xor(post_max, d));
-      pinc += __shfl_xor(pinc, d);
+      if constexpr (RPI == 2) pinc += __shfl_xor(pinc, d);
     }
     if (lane == 0 && pre_max) atomicMax(&s.ctl[kCtlPreMax], pre_max);
     if (lane == 0 && post_max) atomicMax(&s.ctl[kCtlPostMax], post_max);
     const uint32_t total = __shfl(incl, 63);
+    unsigned long long* slots = pieces;
+    if constexpr (RPI == 2) {
+      if (!s.one_shot) {
+        slots = reinterpret_cast<unsigned long long*>(s.ctl + kCtlTasks);
+        if (lane == 0 && pinc) atomicAdd(pieces, (unsigned long long)pinc);
+      }
+    }
     unsigned long long base = 0;
-    if (lane == 63 && total) base = atomicAdd(s.one_shot ? pieces : count, (unsigned long long)total);
-    if (lane == 0 && pinc && !s.one_shot) atomicAdd(pieces, (unsigned long long)pinc);
+    if (lane == 63 && total) base = atomicAdd(slots, (unsigned long long)total);
     base = __shfl(base, 63);
-    uint64_t at = base + incl - k;
-    if (s.one_shot) {
-      if (i < n) {  // range records at fixed slots, their pieces at `at`
-        s.tasks[2 * i] = ApplyTask{pdst, psrc, (uint32_t)plen, (uint32_t)i, wval, (uint32_t)at | (verify << 31)};
-        s.tasks[2 * i + 1] = ApplyTask{gdst, 0, (uint32_t)glen, (uint32_t)i, wval, (uint32_t)(at + pp) | (verify << 31)};
+    uint64_t at = base + incl - cnt_io;
+    if constexpr (RPI == 2) {
+      if (!s.one_shot) {  // the ticketed tasks: the payload's pieces, then the gap's
+#pragma unroll
+        for (uint32_t k = 0; k < 2; ++k)
+          for (uint32_t j = 0; j < tk[k]; ++j) {
+            uint64_t a, b;
+            piece_bounds(R[k].dst, R[k].len, j, s.pieces, s.piece_min, a, b);
+            s.tasks[at++] = ApplyTask{R[k].dst + a, R[k].src ? R[k].src + a : 0, (uint32_t)(b - a), (uint32_t)i, wval, verify};
+          }
+        continue;
       }
-      // the piece table, one IO at a time by the whole wave (coalesced rows; a lane writing
-      // its own IO's entries hit 64 lines per store and doubled the prep launch)
-      // (readlane, not __shfl: an LDS round trip per step made this loop latency-bound)
-      for (uint32_t l = 0; l < 64; ++l) {  // wave-uniform
-        const uint32_t cnt = __builtin_amdgcn_readlane(pp + pg, l), ppl = __builtin_amdgcn_readlane(pp, l);
-        if (!cnt) continue;
-        const uint64_t atl = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)at, l) |
-                             (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(at >> 32), l) << 32;
-        const uint32_t r = (uint32_t)(2 * (i0 + l));
-        for (uint32_t j = lane; j < cnt; j += 64) s.ptab[atl + j] = r + (j >= ppl ? 1u : 0u);
+    }
+    if (i < n) {  // range records at fixed slots, their pieces at `at`
+      // (a range of length 0 is stored as {0, 0, 0}: it has no piece, so no table entry names it)
+#pragma unroll
+      for (uint32_t k = 0; k < RPI; ++k)
+        s.tasks[RPI * i + k] =
+            ApplyTask{R[k].dst, R[k].src, R[k].len, (uint32_t)i, wval, (uint32_t)(at + before[k]) | (verify << 31)};
+    }
+    // the piece table, one IO at a time by the whole wave (coalesced rows; a lane writing
+    // its own IO's entries hit 64 lines per store and doubled the prep launch)
+    // (readlane, not __shfl: an LDS round trip per step made this loop latency-bound)
+    for (uint32_t l = 0; l < 64; ++l) {  // wave-uniform
+      const uint32_t cnt = __builtin_amdgcn_readlane(before[RPI], l);
+      if (!cnt) continue;
+      uint32_t bl[RPI];
+#pragma unroll
+      for (uint32_t k = 1; k < RPI; ++k) bl[k] = __builtin_amdgcn_readlane(before[k], l);
+      const uint64_t atl = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)at, l) |
+                           (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(at >> 32), l) << 32;
+      const uint32_t r = (uint32_t)(RPI * (i0 + l));
+      for (uint32_t j = lane; j < cnt; j += 64) {
+        uint32_t rec = r;
+#pragma unroll
+        for (uint32_t k = 1; k < RPI; ++k) rec += j >= bl[k] ? 1u : 0u;
+        s.ptab[atl + j] = rec;
       }
-      continue;
-    }
-    for (uint32_t j = 0; j < np; ++j) {
-      uint64_t a, b;
-      piece_bounds(pdst, plen, j, s, a, b);
-      s.tasks[at++] = ApplyTask{pdst + a, psrc + a, (uint32_t)(b - a), (uint32_t)i, wval, verify};
-    }
-    for (uint32_t j = 0; j < ng; ++j) {
-      uint64_t a, b;
-      piece_bounds(gdst, glen, j, s, a, b);
-      s.tasks[at++] = ApplyTask{gdst + a, 0, (uint32_t)(b - a), (uint32_t)i, wval, verify};
     }
   }
   // the launch's extra workgroup (place_runs): the pre hash's byte runs
-  if (place_runs && blockIdx.x == gridDim.x - 1)
-    bal_runs_block(ios, (uint32_t)n, max_len, type, mode, s.run_waves, s.run_bal, s.run_boff);
-}
-
-// prep of hf3fs_crc_update_cow_batch (one-shot apply only): as k_update_prep, with IO i's image
-// written at plan_image(chunk, dsts[i]) and kPlanRanges range records per IO at tasks[4 i + k]
-// (update_plan.h plan_ranges: payload, gap, old prefix, old suffix).  Every record carries the
-// IO's verify bit -- a failed payload verify copies no old byte either -- and ptab[p] is the
-// record of piece p, an IO's pieces in record order.  dsts may be null (every IO in place).
-__global__ __launch_bounds__(kPrepThreads) void k_update_prep_cow(hf3fs_crc_update_io* __restrict__ ios,
-                                                                  const uint64_t* __restrict__ dsts, uint64_t n,
-                                                                  uint32_t max_len, uint8_t type, int mode,
-                                                                  UpdateScratch s, int place_runs) {
-  const uint32_t lane = threadIdx.x & 63;
-  unsigned long long* pieces = reinterpret_cast<unsigned long long*>(s.ctl + kCtlPieces);
-  for (uint64_t i0 = (uint64_t)blockIdx.x * kPrepIoThreads + (threadIdx.x & ~63u);
-       threadIdx.x < kPrepIoThreads && i0 < n; i0 += (uint64_t)gridDim.x * kPrepIoThreads) {
-    const uint64_t i = i0 + lane;
-    PlanRange R[kPlanRanges] = {};
-    uint32_t wval = 0, verify = 0, pre_max = 0, post_max = 0;
-    if (i < n) {
-      const hf3fs_crc_update_io io = ios[i];
-      const uint64_t image = plan_image(io.chunk, dsts ? dsts[i] : 0);
-      const Eff e = prep_one<true>(ios, i, max_len, type, mode, s, pre_max, post_max, image);
-      plan_ranges(io, e, image, R);
-      if (e.ok) {
-        wval = e.wval;
-        verify = e.verify;
-      }
-    }
-    uint32_t before[kPlanRanges + 1];  // pieces of the IO's earlier ranges
-    before[0] = 0;
-#pragma unroll
-    for (int k = 0; k < kPlanRanges; ++k) before[k + 1] = before[k] + pieces_of(R[k].dst, R[k].len, s.piece_shift);
-    const uint32_t cnt_io = before[kPlanRanges];
-    uint32_t incl = cnt_io;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(incl, d);
-      if (lane >= (uint32_t)d) incl += y;
-      pre_max = max(pre_max, (uint32_t)__shfl_xor(pre_max, d));
-      post_max = max(post_max, (uint32_t)__shfl_xor(post_max, d));
-    }
-    if (lane == 0 && pre_max) atomicMax(&s.ctl[kCtlPreMax], pre_max);
-    if (lane == 0 && post_max) atomicMax(&s.ctl[kCtlPostMax], post_max);
-    const uint32_t total = __shfl(incl, 63);
-    unsigned long long base = 0;
-    if (lane == 63 && total) base = atomicAdd(pieces, (unsigned long long)total);
-    base = __shfl(base, 63);
-    const uint64_t at = base + incl - cnt_io;
-    if (i < n) {
-#pragma unroll
-      for (int k = 0; k < kPlanRanges; ++k)
-        s.tasks[kPlanRanges * i + k] =
-            ApplyTask{R[k].dst, R[k].src, R[k].len, (uint32_t)i, wval, (uint32_t)(at + before[k]) | (verify << 31)};
-    }
-    for (uint32_t l = 0; l < 64; ++l) {  // wave-uniform: one IO's table rows at a time, coalesced
-      const uint32_t cnt = __builtin_amdgcn_readlane(cnt_io, l);
-      if (!cnt) continue;
-      const uint32_t b1 = __builtin_amdgcn_readlane(before[1], l), b2 = __builtin_amdgcn_readlane(before[2], l),
-                     b3 = __builtin_amdgcn_readlane(before[3], l);
-      const uint64_t atl = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)at, l) |
-                           (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(at >> 32), l) << 32;
-      const uint32_t r = (uint32_t)(kPlanRanges * (i0 + l));
-      for (uint32_t j = lane; j < cnt; j += 64)
-        s.ptab[atl + j] = r + (j >= b1 ? 1u : 0u) + (j >= b2 ? 1u : 0u) + (j >= b3 ? 1u : 0u);
-    }
-  }
   if (place_runs && blockIdx.x == gridDim.x - 1)
     bal_runs_block(ios, (uint32_t)n, max_len, type, mode, s.run_waves, s.run_bal, s.run_boff);
 }
@@ -1032,14 +939,20 @@ uint64_t update_cow_piece_cap(uint64_t n, uint32_t max_len, uint32_t piece_shift
   return n * plan_piece_bound(max_len, piece_shift, kPlanRanges);
 }
 
-size_t update_scratch_bytes(uint64_t n, uint32_t pieces, uint32_t nw, uint64_t ptab_cap) {
-  const uint64_t tasks = n * 2 * (uint64_t)(pieces + 1);
-  const uint64_t runs = kRunBlocksMax * 8 + (nw + 1) * (4 + 8);
-  return n * 2 * (8 + 8 + 4 + 4) * 2 + tasks * sizeof(ApplyTask) + kCtlWords * 4 + runs + ptab_cap * 4 + 1024;
+// The record array of a call: rpi range records per IO (one-shot apply), or the ticketed apply's
+// tasks -- payload and gap, each at most pieces + 1 tasks (update_plan.h piece_count <= pieces + 1,
+// checked by tests/cpp/fuzz_cow_planner.cpp) -- whichever is more.  pieces = 0: no ticketed apply.
+uint64_t update_record_cap(uint64_t n, uint32_t rpi, uint32_t pieces) {
+  return n * std::max<uint64_t>(rpi, 2 * (uint64_t)(pieces + 1));
 }
 
-void update_scratch_carve(void* base, uint64_t n, uint32_t pieces, uint32_t piece_min, uint32_t nw,
-                          uint64_t ptab_cap, UpdateScratch* s) {
+size_t update_scratch_bytes(uint64_t n, uint64_t records, uint32_t nw, uint64_t ptab_cap) {
+  const uint64_t runs = kRunBlocksMax * 8 + (nw + 1) * (4 + 8);
+  return n * 2 * (8 + 8 + 4 + 4) * 2 + records * sizeof(ApplyTask) + kCtlWords * 4 + runs + ptab_cap * 4 + 1024;
+}
+
+void update_scratch_carve(void* base, uint64_t n, uint64_t records, uint32_t pieces, uint32_t piece_min,
+                          uint32_t nw, uint64_t ptab_cap, UpdateScratch* s) {
   uint8_t* p = (uint8_t*)base;
   auto take = [&](size_t bytes) {
     uint8_t* r = p;
@@ -1055,7 +968,7 @@ void update_scratch_carve(void* base, uint64_t n, uint32_t pieces, uint32_t piec
   s->post_len = (uint64_t*)take(2 * n * 8);
   s->post_start = (uint32_t*)take(2 * n * 4);
   s->post_out = (uint32_t*)take(2 * n * 4);
-  s->tasks = (ApplyTask*)take(n * 2 * (uint64_t)(pieces + 1) * sizeof(ApplyTask));
+  s->tasks = (ApplyTask*)take(records * sizeof(ApplyTask));
   s->pieces = pieces;
   s->piece_min = piece_min;
   s->ptab = (uint32_t*)take(ptab_cap * 4);
@@ -1071,24 +984,17 @@ void update_scratch_carve(void* base, uint64_t n, uint32_t pieces, uint32_t piec
   s->fault_io = 0;
 }
 
-hipError_t launch_update_prep(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max_len, uint8_t type, int mode,
-                              const UpdateScratch& s, bool place_runs, hipStream_t st) {
+hipError_t launch_update_prep(hf3fs_crc_update_io* ios, const uint64_t* dsts, uint64_t n, uint32_t max_len,
+                              uint8_t type, int mode, const UpdateScratch& s, uint32_t rpi, bool place_runs,
+                              hipStream_t st) {
   // place_runs (2n <= kPrepRunJobs, so one pass of the IO loop): one more workgroup for the runs.
   // 1024-thread workgroups: the runs workgroup derives 4 IOs per thread (with 256 threads it
   // took 30 us, the 16 IOs per thread of derive + pre_lens on one wave per SIMD).
   const uint64_t want = (n + kPrepIoThreads - 1) / kPrepIoThreads;
   const unsigned grid = (unsigned)(want < 1024 ? (want ? want : 1) : 1024);
-  hipLaunchKernelGGL(k_update_prep, dim3(grid + (place_runs ? 1 : 0)), dim3(kPrepThreads), 0, st, ios, n, max_len,
+  const auto kernel = rpi == 2 ? k_update_prep<2> : k_update_prep<kPlanRanges>;
+  hipLaunchKernelGGL(kernel, dim3(grid + (place_runs ? 1 : 0)), dim3(kPrepThreads), 0, st, ios, dsts, n, max_len,
                      type, mode, s, place_runs ? 1 : 0);
-  return hipGetLastError();
-}
-
-hipError_t launch_update_prep_cow(hf3fs_crc_update_io* ios, const uint64_t* dsts, uint64_t n, uint32_t max_len,
-                                  uint8_t type, int mode, const UpdateScratch& s, bool place_runs, hipStream_t st) {
-  const uint64_t want = (n + kPrepIoThreads - 1) / kPrepIoThreads;
-  const unsigned grid = (unsigned)(want < 1024 ? (want ? want : 1) : 1024);
-  hipLaunchKernelGGL(k_update_prep_cow, dim3(grid + (place_runs ? 1 : 0)), dim3(kPrepThreads), 0, st, ios, dsts, n,
-                     max_len, type, mode, s, place_runs ? 1 : 0);
   return hipGetLastError();
 }
 
@@ -1115,15 +1021,9 @@ static void launch_one_shot(uint64_t n, const UpdateScratch& s, uint32_t grid, i
 #undef HF3FS_ONE_SHOT
 }
 
-hipError_t launch_update_apply_cow(uint64_t n, const UpdateScratch& s, uint32_t grid, int nt, uint64_t ptab_cap,
-                                   uint64_t* hint, hipStream_t st) {
-  launch_one_shot<kPlanRanges>(n, s, grid, nt, ptab_cap, hint, st);
-  return hipGetLastError();
-}
-
 hipError_t launch_update_apply(hf3fs_crc_update_io* ios, uint64_t n, uint32_t max_len, uint8_t type, int mode,
-                               const UpdateScratch& s, const DeviceTables* tabs, bool finalize_delta, uint32_t grid,
-                               int nt, uint64_t ptab_cap, uint64_t* hint, hipStream_t st) {
+                               const UpdateScratch& s, const DeviceTables* tabs, uint32_t rpi, bool finalize_delta,
+                               uint32_t grid, int nt, uint64_t ptab_cap, uint64_t* hint, hipStream_t st) {
   // U = 4 granules in flight per thread, cached loads/stores, one aligned load per misaligned
   // granule + a lane shift, 1 KiB-aligned store rows: the A/Bs of DESIGN.md 3.2 and the copy
   // probe (profiles/r03_probe_copy.log: every copy form measured within 5 % of this one).
@@ -1145,9 +1045,11 @@ hipError_t launch_update_apply(hf3fs_crc_update_io* ios, uint64_t n, uint32_t ma
     case 7: HF3FS_APPLY(P, true, true, true); break;    \
     default: HF3FS_APPLY(P, false, false, false);       \
   }
-  if (s.one_shot) {
+  if (s.one_shot && rpi == kPlanRanges) {
+    launch_one_shot<kPlanRanges>(n, s, grid, nt, ptab_cap, hint, st);
+  } else if (s.one_shot) {
     launch_one_shot<2>(n, s, grid, nt, ptab_cap, hint, st);
-  } else if (type == kTypeCrc32) {
+  } else if (type == kTypeCrc32) {  // (ticketed: 2 records per IO only)
     HF3FS_APPLY_NT(kPolyCrc32)
   } else {
     HF3FS_APPLY_NT(kPolyCrc32c)

@@ -1,16 +1,19 @@
 // update_plan.h -- the planner arithmetic of the update path, plain C++ that both the device
-// compiler and a host compiler take: what ChunkReplica::update / the chunk engine make of one
-// IO (derive), which byte ranges the apply moves for it and where (plan_ranges), and where the
-// one-shot apply cuts a range into pieces (pieces_of, piece_span).  Who calls what:
-//   derive, pieces_of      every prep kernel;
-//   piece_span             the one-shot apply (one_shot_piece), in place and with destinations;
-//   plan_ranges            k_update_prep_cow only.  The in-place k_update_prep keeps its own two
-//                          lines for the payload and gap {dst, src, len} (it was not to change);
-//                          plan_ranges with image == chunk states the same two ranges.
-// So for hf3fs_crc_update_cow_batch nothing else decides an address, and the rule "every piece
-// lies inside [dst, dst + out_size) and the pieces of an IO tile its image exactly once" is
-// checked on the CPU (tests/cpp/fuzz_cow_planner.cpp, under ASan + UBSan); for the in-place
-// kernel that program checks derive and the piece cuts, and plan_ranges as a restatement of it.
+// compiler and a host compiler take.  Every address and every count of the path is decided here:
+// what ChunkReplica::update / the chunk engine make of one IO (derive), the hash jobs before and
+// after the write (pre_lens, plan_jobs), which byte ranges the apply moves and where (plan_ranges),
+// where the one-shot apply cuts a range (pieces_of, piece_span) and where the ticketed apply does
+// (piece_bytes, piece_count, piece_bounds).  Who calls what:
+//   derive, pre_lens       prep (prep_one and the runs workgroup), finalize, the fused kernel;
+//   plan_jobs              prep_one, which only stores the four jobs;
+//   plan_ranges, pieces_of k_update_prep<RPI>, in place (RPI = 2: image == chunk, the payload and
+//                          gap records) and with destinations (RPI = kPlanRanges);
+//   piece_count / _bounds  k_update_prep<2>'s ticketed emission;
+//   piece_span             the one-shot apply (one_shot_piece).
+// The kernels keep no address arithmetic of their own, so the rules "every piece lies inside
+// [dst, dst + out_size), the pieces of an IO tile its image exactly once, every job reads inside
+// its buffer" are checked on the CPU for every entry point (tests/cpp/fuzz_cow_planner.cpp, under
+// ASan + UBSan).
 #pragma once
 #include <stdint.h>
 
@@ -135,6 +138,49 @@ HF3FS_PLAN_FN Eff derive(const hf3fs_crc_update_io& io, uint32_t max_len, uint8_
 // destination of its own (hf3fs_crc_update_cow_batch: d_dst[i], 0 = none).
 HF3FS_PLAN_FN uint64_t plan_image(uint64_t chunk, uint64_t dst) { return dst ? dst : chunk; }
 
+// Lengths of an IO's two pre jobs: the payload (verify) and, for the delta method, the old
+// bytes under the write or the truncated tail.  Only the IO's input fields and Eff.
+HF3FS_PLAN_FN void pre_lens(const Eff& e, uint64_t& l0, uint64_t& l1) {
+  l0 = l1 = 0;
+  if (!e.ok) return;
+  if (e.hash_payload) l0 = e.len;
+  if (e.kase == 4 && e.delta) {
+    if (!e.te && e.off < e.s0)
+      l1 = (e.off + e.len < e.s0 ? e.off + e.len : e.s0) - e.off;
+    else if (e.te && e.s1 < e.s0)
+      l1 = e.s0 - e.s1;
+  }
+}
+
+// The hash jobs of one IO whose image is written at `image`.  Before the write ("pre"):
+//   [0] payload    payload[0, len)
+//   [1] old bytes  chunk[off, min(off + len, s0)), a truncate's chunk[s1, s0)   (delta method)
+// After it ("post", the reference method's recompute, ChunkReplica.cc:356-389):
+//   [2] prefix     image[0, off)       (holds the zero-filled gap of a write past the size)
+//   [3] suffix     image[min(off + len, s1), s1)
+// The pre jobs read the committed chunk whatever the image; a job of length 0 has address 0, and
+// an IO that is not ok has none.
+struct PlanJob {
+  uint64_t addr, len;
+};
+enum { kJobPayload = 0, kJobOld = 1, kJobPrefix = 2, kJobSuffix = 3, kPlanJobs = 4 };
+struct PlanJobs {
+  PlanJob job[kPlanJobs];
+};
+
+HF3FS_PLAN_FN PlanJobs plan_jobs(const hf3fs_crc_update_io& io, const Eff& e, uint64_t image) {
+  PlanJobs J{};
+  pre_lens(e, J.job[kJobPayload].len, J.job[kJobOld].len);
+  if (J.job[kJobPayload].len) J.job[kJobPayload].addr = io.payload;
+  if (J.job[kJobOld].len) J.job[kJobOld].addr = io.chunk + (e.te ? e.s1 : e.off);
+  if (e.ok && e.kase == 4 && !e.delta) {
+    const uint32_t suffix_start = e.off + e.len < e.s1 ? e.off + e.len : e.s1;
+    J.job[kJobPrefix] = PlanJob{image, e.off};
+    J.job[kJobSuffix] = PlanJob{image + suffix_start, e.s1 - suffix_start};
+  }
+  return J;
+}
+
 // The byte ranges the apply moves for one IO whose image is written at `image`:
 //   [0] payload  image[off, off + len)            <- payload
 //   [1] gap      image[zero_from, zero_to)        <- 0   (write past the size; an extend's extension)
@@ -180,6 +226,28 @@ HF3FS_PLAN_FN void piece_span(uint64_t dst, uint64_t len, uint32_t shift, uint64
   const uint64_t cut = (dst & ~(P - 1)) + (j << shift);
   a = cut > dst ? cut : dst;
   e = cut + P < dst + len ? cut + P : dst + len;
+}
+
+// Ticketed apply pieces of a range of len bytes at dst: at most `pieces` even shares of at least
+// piece_min bytes, cut at 16-byte aligned destination addresses.  With h = dst & 15 and ps =
+// piece_bytes, piece j = [max(0, j ps - h), min(len, (j + 1) ps - h)).  len <= pieces * ps and
+// ps > 15, so a range has at most pieces + 1 of them (the + 1 is the alignment of the cuts).
+HF3FS_PLAN_FN uint64_t piece_bytes(uint64_t len, uint32_t pieces, uint32_t piece_min) {
+  const uint64_t even = ((len + pieces - 1) / pieces + 15) & ~uint64_t(15);
+  return even > piece_min ? even : piece_min;
+}
+HF3FS_PLAN_FN uint32_t piece_count(uint64_t dst, uint64_t len, uint32_t pieces, uint32_t piece_min) {
+  if (!len) return 0;
+  const uint64_t ps = piece_bytes(len, pieces, piece_min);
+  return (uint32_t)(((dst & 15) + len + ps - 1) / ps);
+}
+// Piece j (< piece_count) of the range: bytes [a, b) of it.
+HF3FS_PLAN_FN void piece_bounds(uint64_t dst, uint64_t len, uint32_t j, uint32_t pieces, uint32_t piece_min,
+                                uint64_t& a, uint64_t& b) {
+  const uint64_t ps = piece_bytes(len, pieces, piece_min), h = dst & 15;
+  a = j ? (uint64_t)j * ps - h : 0;
+  const uint64_t b0 = (uint64_t)(j + 1) * ps - h;
+  b = b0 < len ? b0 : len;
 }
 
 // Piece-table entries one IO can need, in place (payload + gap) and with a destination (all four

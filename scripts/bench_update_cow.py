@@ -11,8 +11,12 @@ warm-up, timed with stream events around `--calls` calls:
            destination.
   inplace  the in-place path of this build against another build of the library (--parent-lib,
            loaded beside it): bench.py's headline (create_strided over 4096 x 4 MiB), d3 DELTA
-           update_batch and a latency-bound batch of 256 of its IOs, the two libraries
-           alternating, `--runs` runs each.
+           update_batch, a latency-bound batch of 256 of its IOs and the out-of-place variant A
+           (update_cow_batch), the two libraries alternating, `--runs` runs each.  Before the
+           timing one line per (n, max_len, mode) with what the three *_scratch_bytes functions
+           of either library return ("equal": the builds ask for the same bytes).
+  d3loop   d3 DELTA update_batch alone, `--runs` x `--calls` calls of the library this process loaded
+           (HF3FS_CRC_LIB names another build): the loop a kernel trace of one build is taken of.
   syncing  a whole-chunk resync batch (4096 x 4 MiB, syncing, out of place) vs verify_strided of
            the payloads plus one copy of the same bytes.  For the record only.
 
@@ -99,7 +103,7 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "update_cow_ab.jsonl"))
-    ap.add_argument("--only", choices=["cow", "inplace", "syncing"], default=None)
+    ap.add_argument("--only", choices=["cow", "inplace", "syncing", "d3loop"], default=None)
     ap.add_argument("--parent-lib", default=None, help="another build of libhf3fs_crc.so for the in-place A/B")
     ap.add_argument("--branch-first", action="store_true", help="in-place A/B: this build takes the first turn")
     ap.add_argument("--variants", default=None, help="comma list of cow variants to time (a kernel trace of one)")
@@ -227,16 +231,39 @@ def main():
                                   calls=a.calls, correct=good))
             del ios_s
 
+        # ---- d3loop: the in-place d3 batch of the loaded library, for a kernel trace ---------------------------
+        if a.only == "d3loop":
+            ios = dev_records(records(src_addr, offs, lens, pck), dev)
+            t = alternate({os.path.basename(os.environ.get("HF3FS_CRC_LIB") or "branch"):
+                           lambda: L.update_batch(hf.CRC32C, ios, N, CHUNK, mode=mode, stream=s)}, a.runs, a.calls, s)
+            for k, v in t.items():
+                lines.append(line("d3loop", k, shape, v, box, calls=a.calls))
+
         # ---- inplace: this build against another one ---------------------------------------------------------------
         if a.only in (None, "inplace") and a.parent_lib:
-            if a.only is None:
-                del dest
+            if a.only is not None:
+                dest = torch.zeros(N * CHUNK, dtype=torch.uint8, device=dev)
+                dst_addr = (dest.data_ptr() + np.arange(N) * CHUNK).astype(np.uint64)
+                d_dst = torch.tensor(dst_addr.view(np.int64), device=dev)
             other = ctypes.CDLL(a.parent_lib)
-            for name in ("hf3fs_crc_update_batch", "hf3fs_crc_create_strided"):
+            sizing = ("hf3fs_crc_update_scratch_bytes", "hf3fs_crc_update_ordered_scratch_bytes",
+                      "hf3fs_crc_update_cow_scratch_bytes")
+            for name in ("hf3fs_crc_update_batch", "hf3fs_crc_create_strided", "hf3fs_crc_update_cow_batch") + sizing:
                 res, args = L.SIGNATURES[name]
                 getattr(other, name).restype, getattr(other, name).argtypes = res, args
             mine = L.load()
+            # the scratch a call asks for, both builds: (n, max_len) x mode x the three sizing functions
+            for n_, ml in ((1, 4 << 10), (256, 1 << 20), (4096, 4 << 20)):
+                for m in (hf.MODE_REFERENCE, hf.MODE_DELTA):
+                    got = {k: [int(lib.hf3fs_crc_update_scratch_bytes(n_, m)),
+                               int(lib.hf3fs_crc_update_ordered_scratch_bytes(n_, ml, m, 4)),
+                               int(lib.hf3fs_crc_update_cow_scratch_bytes(n_, ml, m))]
+                           for k, lib in (("parent", other), ("branch", mine))}
+                    lines.append({"bench": "scratch_bytes", "n": n_, "max_len": ml, "mode": int(m),
+                                  "functions": [f[len("hf3fs_crc_"):] for f in sizing], "parent": got["parent"],
+                                  "branch": got["branch"], "equal": got["parent"] == got["branch"], "box": box})
             ios = dev_records(records(src_addr, offs, lens, pck), dev)
+            ios_cow = dev_records(records(src_addr, offs, lens, pck), dev)  # chunk = the old version, image in dest
             out = torch.zeros(N, dtype=torch.int32, device=dev)
             st = s.cuda_stream
 
@@ -250,14 +277,20 @@ def main():
             def small(lib):  # a latency-bound batch: the first 256 records (prep, hashes and apply barely fill the chip)
                 return lambda: lib.hf3fs_crc_update_batch(hf.CRC32C, ios.data_ptr(), 256, CHUNK, mode, st)
 
-            for bench, make in (("inplace_d3_delta", d3), ("inplace_small_delta", small), ("inplace_headline", headline)):
+            def cow(lib):  # variant A of the cow section: d3's batch out of place
+                return lambda: lib.hf3fs_crc_update_cow_batch(hf.CRC32C, ios_cow.data_ptr(), d_dst.data_ptr(), N, CHUNK,
+                                                              mode, st)
+
+            for bench, make in (("inplace_d3_delta", d3), ("inplace_small_delta", small), ("inplace_headline", headline),
+                                ("cow_d3_delta", cow)):
                 pair = {"parent": make(other), "branch": make(mine)}
                 if a.branch_first:
                     pair = dict(reversed(list(pair.items())))
                 t = alternate(pair, a.runs, a.calls, s)
                 for k, v in t.items():
                     what = {"inplace_d3_delta": shape, "inplace_small_delta": "256 of those IOs, DELTA",
-                            "inplace_headline": "create_strided 4096 x 4 MiB"}[bench]
+                            "inplace_headline": "create_strided 4096 x 4 MiB",
+                            "cow_d3_delta": shape + ", update_cow_batch out of place"}[bench]
                     lines.append(line(bench, k, what, v, box, calls=a.calls, first_turn=next(iter(pair)), gb_per_s=round(N * CHUNK / statistics.median(v) / 1e6, 1)
                                       if bench.endswith("headline") else None))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

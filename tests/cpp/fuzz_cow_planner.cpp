@@ -9,6 +9,18 @@
 //   invalid IOs:             nothing (a failed payload verify is the apply kernel's business: every
 //                            record of the IO must carry the verify bit's condition, checked here).
 // Every byte is written at most once, and the piece counts stay inside plan_piece_bound.
+// The in-place records of hf3fs_crc_update_batch are literally plan_ranges(..., image == chunk)
+// -- k_update_prep<2> has no lines of its own for them -- so the in-place model check covers
+// that kernel's addresses too.  Beside the records, for every IO:
+//   jobs      plan_jobs, the four hash jobs prep stores: the payload job is [payload, payload +
+//             length), the old-byte job lies inside [chunk, chunk + s0), both post jobs inside
+//             [image, image + s1), and an IO that is not ok has none;
+//   tickets   the ticketed apply's cuts (piece_count / piece_bounds) for pieces in [1, 64] and
+//             piece_min a multiple of 1 KiB (the ranges options.cc admits), every destination
+//             residue mod 16, lengths around 0, 16, piece_min and pieces * piece_min: the pieces
+//             tile [0, len) exactly once and in order, every cut but the first lies on a 16-byte
+//             aligned destination address, and piece_count <= pieces + 1 -- the bound the record
+//             array's size rests on (update_record_cap).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -64,11 +76,51 @@ uint32_t pick_len(uint32_t limit, uint32_t P, uint64_t at) {
   return v > limit ? limit : v;
 }
 
+[[noreturn]] void die_ticket(const char* what, uint64_t it, uint64_t dst, uint64_t len, uint32_t pieces,
+                             uint32_t piece_min, long long x) {
+  std::printf("{\"fuzz_cow_planner\":\"FAIL\",\"what\":\"%s\",\"iteration\":%llu,\"dst\":%llu,\"len\":%llu,"
+              "\"pieces\":%u,\"piece_min\":%u,\"x\":%lld}\n",
+              what, (unsigned long long)it, (unsigned long long)dst, (unsigned long long)len, pieces, piece_min, x);
+  std::exit(1);
+}
+
+// The ticketed apply's cuts of one range, as k_update_prep<2> emits them; returns the piece count.
+uint32_t check_tickets(uint64_t it, uint64_t dst, uint64_t len, uint32_t pieces, uint32_t piece_min) {
+  const uint32_t np = piece_count(dst, len, pieces, piece_min);
+  if ((len == 0) != (np == 0)) die_ticket("empty range with tickets", it, dst, len, pieces, piece_min, np);
+  if (np > pieces + 1) die_ticket("ticket bound", it, dst, len, pieces, piece_min, np);
+  uint64_t prev = 0;
+  for (uint32_t j = 0; j < np; ++j) {
+    uint64_t a, b;
+    piece_bounds(dst, len, j, pieces, piece_min, a, b);
+    if (a != prev || b <= a || b > len) die_ticket("tickets do not tile the range", it, dst, len, pieces, piece_min, j);
+    if (j && ((dst + a) & 15)) die_ticket("ticket cut off a 16-byte line", it, dst, len, pieces, piece_min, j);
+    prev = b;
+  }
+  if (prev != len) die_ticket("tickets short of the range", it, dst, len, pieces, piece_min, (long long)prev);
+  return np;
+}
+
+// a length around 0, 16, piece_min or pieces * piece_min, or anywhere below 2^32
+uint64_t pick_ticket_len(uint32_t pieces, uint32_t piece_min) {
+  uint64_t v;
+  switch (below(6)) {
+    case 0: v = below(3); break;
+    case 1: v = 14 + below(20); break;
+    case 2: v = (uint64_t)piece_min * (1 + below(2)) + below(35) - 17; break;
+    case 3: v = (uint64_t)pieces * piece_min + below(35) - 17; break;
+    case 4: v = (uint64_t)pieces * piece_min * (1 + below(3)) + below(1u << 20); break;
+    default: v = rnd() >> (32 + below(32));
+  }
+  return v > 0xffffffffull ? 0xffffffffull : v;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   const uint64_t iterations = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 300000;
   uint64_t n_ok = 0, n_bad = 0, n_pieces = 0, n_oop = 0, n_sync = 0, n_big = 0;
+  uint64_t n_pre_jobs = 0, n_post_jobs = 0, n_tickets = 0, n_ticket_full = 0;  // (full: a range of pieces + 1 tickets)
   uint64_t residues[3] = {0, 0, 0};  // bit r set: residue r mod 16 seen for chunk / image / payload
   std::vector<uint32_t> map, model;
   for (uint64_t it = 0; it < iterations; ++it) {
@@ -211,15 +263,51 @@ int main(int argc, char** argv) {
     n_pieces += pieces_io;
     for (size_t x = 0; x < map.size(); ++x)
       if (map[x] != model[x]) die("image differs from the model", it, io, image, shift, (long long)x - kGuard);
+
+    // ---- the hash jobs prep stores ------------------------------------------------------------
+    const PlanJobs J = plan_jobs(io, e, image);
+    uint64_t l0, l1;
+    pre_lens(e, l0, l1);  // (the runs workgroup takes the lengths from here)
+    if (l0 != J.job[kJobPayload].len || l1 != J.job[kJobOld].len) die("pre_lens differs from plan_jobs", it, io, image, shift, 0);
+    for (int k = 0; k < kPlanJobs; ++k) {
+      const PlanJob& j = J.job[k];
+      if (!j.len) {
+        if (j.addr && k < kJobPrefix) die("empty pre job with an address", it, io, image, shift, k);
+        continue;
+      }
+      if (!ok) die("job of an invalid IO", it, io, image, shift, k);
+      const uint64_t lo = k == kJobPayload ? io.payload : k == kJobOld ? io.chunk : image;
+      const uint64_t hi = lo + (k == kJobPayload ? io.length : k == kJobOld ? s0 : out_size);
+      if (j.addr < lo || j.addr + j.len > hi) die("job outside its buffer", it, io, image, shift, k);
+      if (k == kJobPayload && (j.addr != io.payload || j.len != io.length)) die("payload job is not the payload", it, io, image, shift, k);
+      (k < kJobPrefix ? n_pre_jobs : n_post_jobs)++;
+    }
+    if (J.job[kJobPrefix].len + J.job[kJobSuffix].len) {  // the recompute: prefix, payload and suffix tile [0, s1)
+      if (J.job[kJobPrefix].addr != image || J.job[kJobPrefix].len != e.off) die("prefix job", it, io, image, shift, 0);
+      if (J.job[kJobSuffix].len && J.job[kJobSuffix].addr + J.job[kJobSuffix].len != image + out_size) die("suffix job", it, io, image, shift, 0);
+      if (J.job[kJobPrefix].len + e.len + J.job[kJobSuffix].len != out_size) die("post jobs do not tile the image", it, io, image, shift, 0);
+    }
+
+    // ---- the ticketed apply's cuts: of this IO's in-place records, and of a drawn range --------
+    const uint32_t tpieces = 1 + below(64);
+    const uint32_t tmin = (below(4) ? 1 + below(64) : 1 + below(1u << 20)) << 10;
+    if (!oop) n_tickets += check_tickets(it, R[0].dst, R[0].len, tpieces, tmin) + check_tickets(it, R[1].dst, R[1].len, tpieces, tmin);
+    const uint64_t tdst = (uint64_t(1) << 40) + (rnd() & 0xffffff0) + it % 16;
+    const uint32_t tn = check_tickets(it, tdst, pick_ticket_len(tpieces, tmin), tpieces, tmin);
+    n_tickets += tn;
+    n_ticket_full += tn == tpieces + 1;
   }
   const bool all_res = residues[0] == 0xffff && residues[1] == 0xffff && residues[2] == 0xffff;
-  if (!all_res || !n_ok || !n_bad || !n_oop || !n_sync || !n_big) {
+  if (!all_res || !n_ok || !n_bad || !n_oop || !n_sync || !n_big || !n_pre_jobs || !n_post_jobs || !n_ticket_full) {
     std::printf("{\"fuzz_cow_planner\":\"FAIL\",\"what\":\"coverage\"}\n");
     return 1;
   }
   std::printf("{\"fuzz_cow_planner\":\"ok\",\"ios\":%llu,\"valid\":%llu,\"invalid\":%llu,\"out_of_place\":%llu,"
-              "\"syncing\":%llu,\"pieces\":%llu}\n",
+              "\"syncing\":%llu,\"pieces\":%llu,\"pre_jobs\":%llu,\"post_jobs\":%llu,\"tickets\":%llu,"
+              "\"ranges_of_pieces_plus_1_tickets\":%llu}\n",
               (unsigned long long)iterations, (unsigned long long)n_ok, (unsigned long long)n_bad,
-              (unsigned long long)n_oop, (unsigned long long)n_sync, (unsigned long long)n_pieces);
+              (unsigned long long)n_oop, (unsigned long long)n_sync, (unsigned long long)n_pieces,
+              (unsigned long long)n_pre_jobs, (unsigned long long)n_post_jobs, (unsigned long long)n_tickets,
+              (unsigned long long)n_ticket_full);
   return 0;
 }

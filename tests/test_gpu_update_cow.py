@@ -326,7 +326,7 @@ def test_plain_update_batch_plans_as_before_around_a_cow_call(hf, orc, dev, opts
     What this cannot show: that the COW call leaves the plain call's hint word alone.  A plain
     call planned from the COW call's piece count (four ranges per IO) would only launch a larger
     one-shot grid, whose surplus workgroups exit at once, so no result differs; the separation is
-    by construction (PairState::hint[2], plan_apply_cow) and is not verified here."""
+    by construction (PairState::hint[2], plan_update) and is not verified here."""
     opts("update_pipeline", "unfused")
     plain = fp.rounds_scenario(orc, n=32, max_len=64 << 10, rounds=3, seed=0xE7)
     cow = _main(orc, 64 << 10, 8, "crc32c", 9)
