@@ -1,5 +1,6 @@
 """Write-footprint model of hf3fs_crc_update_batch, shared by tests/test_gpu_update_footprint.py
-(the HIP library) and tests/test_update_footprint_model.py (numpy stand-ins that check the checker).
+(the HIP library) and tests/test_update_footprint_model.py (numpy stand-ins that check the checker);
+tests/stream_queue.py builds its queued rounds from the same scenarios and checkers.
 
 Every buffer the call may touch sits inside a canary -- a never-zero function of the byte
 position that differs between neighbouring bytes and neighbouring 16-byte granules -- so a
@@ -249,9 +250,9 @@ def _diff(got, want):
     return int(d[0]), int(d[-1]), int(d.size)
 
 
-def check_round(scn, k, got_arena, got_pay, got_recbuf, sent_recbuf):
-    """Everything the call may and may not have changed in round k (raises AssertionError)."""
-    r, lay, n = scn.rounds[k], scn.lay, scn.n
+def check_arena(scn, k, got_arena):
+    """The whole chunk arena against the oracle's image after round k."""
+    r, lay = scn.rounds[k], scn.lay
     want = scn.image_after(k)
     assert got_arena.shape == want.shape
     if not np.array_equal(got_arena, want):
@@ -261,16 +262,29 @@ def check_round(scn, k, got_arena, got_pay, got_recbuf, sent_recbuf):
             f"{lay.where(first, r.sizes_after)} (got {int(got_arena[first]):#04x}, want {int(want[first]):#04x}), "
             f"last at {last} = {lay.where(last, r.sizes_after)}; ops {r.ops[_chunk_of(lay, first)]!r} / "
             f"{r.ops[_chunk_of(lay, last)]!r}")
+
+
+def check_payload(scn, k, got_pay):
+    """Round k's payload arena is unchanged."""
     want_pay = scn.payload_image(k)
     if not np.array_equal(got_pay, want_pay):
         first, last, cnt = _diff(got_pay, want_pay)
         raise AssertionError(f"round {k}: payload arena changed in {cnt} bytes, offsets {first}..{last}")
+
+
+def check_records(scn, k, got_recbuf, sent_recbuf, n=None):
+    """Round k's record buffer: both guards and every input field as sent, every output field what
+    the oracle expects.  n: the batch held only the records of chunks 0..n-1 (default: all)."""
+    r = scn.rounds[k]
+    n = scn.n if n is None else n
     nb = n * REC.itemsize
-    for name, sl in (("before", slice(0, REC_GUARD)), ("after", slice(REC_GUARD + nb, None))):
+    assert got_recbuf.shape == sent_recbuf.shape == (2 * REC_GUARD + nb,)
+    for name, sl, edge in (("before", slice(0, REC_GUARD), "in front of the record of chunk 0"),
+                           ("after", slice(REC_GUARD + nb, None), f"behind the record of chunk {n - 1}")):
         if not np.array_equal(got_recbuf[sl], sent_recbuf[sl]):
             first, last, cnt = _diff(got_recbuf[sl], sent_recbuf[sl])
             raise AssertionError(f"round {k}: record guard {name} the array changed in {cnt} bytes, "
-                                 f"guard offsets {first}..{last}")
+                                 f"guard offsets {first}..{last} ({edge})")
     got_b = got_recbuf[REC_GUARD:REC_GUARD + nb].reshape(n, REC.itemsize)
     sent_b = sent_recbuf[REC_GUARD:REC_GUARD + nb].reshape(n, REC.itemsize)
     bad = (got_b != sent_b) & INPUT_MASK[None, :]
@@ -280,17 +294,24 @@ def check_round(scn, k, got_arena, got_pay, got_recbuf, sent_recbuf):
                              f"{int(sent_b[i, byte]):#04x}, got {int(got_b[i, byte]):#04x})")
     res = np.frombuffer(got_b.tobytes(), dtype=REC)
     for c in range(n):
-        e, g, what = r.expect[c], res[c], (k, c, r.ops[c])
-        assert int(g["status"]) == e[0], ("status", what, int(g["status"]), e)
-        assert int(g["checksum_case"]) == e[3], ("case", what, int(g["checksum_case"]), e)
+        e, g, what = r.expect[c], res[c], f"round {k}: chunk {c} {r.ops[c]!r}"
+        assert int(g["status"]) == e[0], (what, "status", int(g["status"]), e)
+        assert int(g["checksum_case"]) == e[3], (what, "case", int(g["checksum_case"]), e)
         if scn.engine:
             if e[0] == OK:
-                assert int(g["out_size"]) == e[1], ("size", what, int(g["out_size"]), e)
-                assert int(g["out_checksum_type"]) == CRC32C, ("type", what)
-                assert (~int(g["out_checksum"])) & M32 == e[2], ("checksum", what, hex(int(g["out_checksum"])), e)
+                assert int(g["out_size"]) == e[1], (what, "size", int(g["out_size"]), e)
+                assert int(g["out_checksum_type"]) == CRC32C, (what, "type")
+                assert (~int(g["out_checksum"])) & M32 == e[2], (what, "checksum", hex(int(g["out_checksum"])), e)
         else:
-            assert int(g["out_size"]) == e[1], ("size", what, int(g["out_size"]), e)
-            assert (int(g["out_checksum_type"]), int(g["out_checksum"])) == tuple(e[2]), ("checksum", what, e)
+            assert int(g["out_size"]) == e[1], (what, "size", int(g["out_size"]), e)
+            assert (int(g["out_checksum_type"]), int(g["out_checksum"])) == tuple(e[2]), (what, "checksum", e)
+
+
+def check_round(scn, k, got_arena, got_pay, got_recbuf, sent_recbuf):
+    """Everything the call may and may not have changed in round k (raises AssertionError)."""
+    check_arena(scn, k, got_arena)
+    check_payload(scn, k, got_pay)
+    check_records(scn, k, got_recbuf, sent_recbuf)
 
 
 def _chunk_of(lay, pos):
