@@ -160,9 +160,10 @@ struct hf3fs_crc_coalescer {
   bool stop = false;
   bool launcher_done = false;
   std::thread launcher, completer;
-  // stats
+  // stats: requests / bytes count every accepted request that has bytes to hash, on every route
+  // (batch path under `mu`; service ring and the create_host route in the two atomics)
   uint64_t n_requests = 0, n_batches = 0, n_bytes = 0, max_batch_seen = 0;
-  std::atomic<uint64_t> n_service{0};
+  std::atomic<uint64_t> n_service{0}, n_service_bytes{0};
   Service* svc = nullptr;
 
   int init();
@@ -305,6 +306,8 @@ int hf3fs_crc_coalescer::submit(uint8_t type, const void* addr, uint64_t len, ui
     int rc = hf3fs_crc_create_host(type, &addr, &len, &start, &out, 1);
     (void)hipSetDevice(prev);
     if (rc) return rc;
+    n_service.fetch_add(1, std::memory_order_relaxed);
+    n_service_bytes.fetch_add(len, std::memory_order_relaxed);
     fn(arg, HF3FS_CRC_OK, out);
     return HF3FS_CRC_OK;
   }
@@ -386,7 +389,9 @@ void hf3fs_crc_coalescer::launcher_loop() {
     s.state = SlotState::kFlying;
     open_next_locked();
     ++n_batches;
-    if (s.total() > max_batch_seen) max_batch_seen = s.total();
+    // per type, the unit of opt.max_batch (a slot holds up to max_batch requests of each type)
+    for (const auto& b : s.sub)
+      if (b.count > max_batch_seen) max_batch_seen = b.count;
     lk.unlock();
     cv_fill.notify_all();  // a fresh slot may be open now
     s.rc = launch(s);
@@ -604,6 +609,7 @@ int hf3fs_crc_coalescer::service_submit(const void* addr, uint64_t len, uint32_t
   }
   service_ensure_running(false);
   n_service.fetch_add(1, std::memory_order_relaxed);
+  n_service_bytes.fetch_add(len, std::memory_order_relaxed);
   *ticket = t;
   return HF3FS_CRC_OK;
 }
@@ -760,7 +766,7 @@ int hf3fs_crc_coalescer_stats(hf3fs_crc_coalescer* c, uint64_t* out4) {
   std::lock_guard<std::mutex> lk(c->mu);
   out4[0] = c->n_requests + c->n_service.load();
   out4[1] = c->n_batches;
-  out4[2] = c->n_bytes;
+  out4[2] = c->n_bytes + c->n_service_bytes.load();
   out4[3] = c->max_batch_seen;
   return HF3FS_CRC_OK;
 }

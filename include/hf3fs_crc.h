@@ -736,7 +736,13 @@ int hf3fs_crc_coalescer_submit(hf3fs_crc_coalescer *co, uint8_t type, const void
 /* Blocking form: returns the submit/batch status, *out = raw value. */
 int hf3fs_crc_coalescer_create_one(hf3fs_crc_coalescer *co, uint8_t type, const void *buf, uint64_t len,
                                    uint32_t start, uint32_t flags, uint32_t *out);
-/* out4 = {requests, batches launched, bytes, largest batch}. */
+/* out4 = {requests, batches launched, bytes, largest batch}.  requests: the accepted requests
+ * that had bytes to hash (a type other than NONE and len > 0), whichever route took them (a
+ * batch launch, the service ring, or hf3fs_crc_create_host for a HOST_COPY request larger than
+ * stage_bytes); a request is counted when its submit call accepts it.  bytes: the sum of their
+ * lengths.  batches launched: hf3fs_crc_create_batch launches (none for the other two routes).
+ * largest batch: the most requests of one type in one launch, in the unit of options.max_batch
+ * and never above it. */
 int hf3fs_crc_coalescer_stats(hf3fs_crc_coalescer *co, uint64_t *out4);
 
 /* Page-lock and map host memory (3FS registers its RDMA BufferPool slabs,

@@ -22,6 +22,9 @@ it is meant to reach:
   buffers / call / extract the device images (inputs, and outputs pre-filled with a sentinel),
                            the library call on their addresses, and the outputs in the
                            reference's form.  No torch here: the GPU test owns the tensors.
+  output_mask / store      per buffer, the bytes include/hf3fs_crc.h lets the call write (the
+                           whole-image check of tests/host_memory.py holds every other byte to
+                           what was sent), and the inverse of extract for numpy stand-ins.
 
 Not here: the >= 1 GiB byte-run forms of create_strided and scrub (test_gpu_parity.py::
 test_create_strided, test_d4_*, test_gpu_aux.py::test_scrub_vs_oracle) and the update path
@@ -97,10 +100,47 @@ class Case:
     records = False       # a record batch (read results, scrub, frames): the anomaly record must stay clean
     poisoned = False      # takes library memory at default switches: part of the poisoned-scratch context
     mutations = ()
+    layouts = {}          # buffer name -> record dtype, for the buffers that are arrays of ABI structs
 
     def device_bytes(self, inp):
         return sum(a.nbytes for a in self.buffers(inp, 1 << 40).values()) + \
             (inp["arena"].nbytes if "arena" in inp else 0)
+
+    def output_mask(self, inp):
+        """{buffer name: boolean byte mask over the buffer's image}, True where include/hf3fs_crc.h
+        lets the call write.  Every buffer of `buffers` has an entry; the arena has none: no call
+        here may write the bytes it hashes.  Each case cites the header lines its mask restates."""
+        raise NotImplementedError
+
+    def store(self, inp, host, ref):
+        """Write `ref` (reference's form) into the output fields of the host images `host`: the
+        inverse of extract, for the stand-in backends of tests/test_host_memory_model.py."""
+        raise NotImplementedError
+
+
+def _masks(images, whole=(), fields=None):
+    """All-False masks over `images`, True for the buffers named in `whole` and, per
+    fields = {buffer: (dtype, field names)}, for the bytes of those fields in every record."""
+    m = {k: np.zeros(a.nbytes, dtype=bool) for k, a in images.items()}
+    for k in whole:
+        if k in m:
+            m[k][:] = True
+    for k, (dt, names) in (fields or {}).items():
+        rec = np.zeros(dt.itemsize, dtype=bool)
+        for f in names:
+            fdt, off = dt.fields[f][:2]
+            rec[off:off + fdt.itemsize] = True
+        m[k] = np.tile(rec, images[k].nbytes // dt.itemsize)
+    return m
+
+
+def field_at(dt, byte):
+    """The field of record dtype `dt` that byte offset `byte` of a record falls in ("padding": none)."""
+    for name in dt.names:
+        fdt, off = dt.fields[name][:2]
+        if off <= byte < off + fdt.itemsize:
+            return name
+    return "padding"
 
 
 # ---- create_batch / verify_batch: a list of ranges ------------------------------------------------
@@ -272,6 +312,15 @@ class ListCase(Case):
         return {k: host[k] for k in (("mismatch", "count", "computed") if self.verify else
                                      [f"out{t}" for t in self.ctypes]) if k in host}
 
+    def output_mask(self, inp):
+        # create_batch: "d_out[i] receives the raw value" (hf3fs_crc.h:161).  verify_batch:
+        # d_mismatch[i], *d_mismatch_count and, when given, d_computed (hf3fs_crc.h:172-174).
+        return _masks(self.buffers(inp, 0), ("mismatch", "count", "computed") + tuple(f"out{t}" for t in self.ctypes))
+
+    def store(self, inp, host, ref):
+        for k, v in ref.items():
+            host[k][:] = v
+
 
 # ---- create_strided / verify_strided --------------------------------------------------------------
 class StridedCase(Case):
@@ -351,6 +400,21 @@ class StridedCase(Case):
             return {k: host[k] for k in ("mismatch", "count", "computed") if k in host}
         return dict(out=np.concatenate([host[f"out{k}"] for k in range(len(inp["geo"]))]))
 
+    def output_mask(self, inp):
+        # create_strided: d_out as create_batch's (hf3fs_crc.h:165-168).  verify_strided: the
+        # outputs of verify_batch (hf3fs_crc.h:172-174, :182-184).
+        return _masks(self.buffers(inp, 0), ("mismatch", "count", "computed") + tuple(f"out{k}" for k in range(3)))
+
+    def store(self, inp, host, ref):
+        if self.verify:
+            for k, v in ref.items():
+                host[k][:] = v
+            return
+        pos = 0
+        for k, g in enumerate(inp["geo"]):
+            host[f"out{k}"][:] = ref["out"][pos:pos + g[0]]
+            pos += g[0]
+
 
 # ---- verify_blocks --------------------------------------------------------------------------------
 def _m_blocks_le_1k(inp, rng):
@@ -408,6 +472,14 @@ class BlocksCase(Case):
 
     def extract(self, inp, host):
         return {k: host[k] for k in ("mismatch", "count", "computed") if k in host}
+
+    def output_mask(self, inp):
+        # "Same outputs as hf3fs_crc_verify_batch" (hf3fs_crc.h:187; :172-174).
+        return _masks(self.buffers(inp, 0), ("mismatch", "count", "computed"))
+
+    def store(self, inp, host, ref):
+        for k, v in ref.items():
+            host[k][:] = v
 
 
 # ---- read results ---------------------------------------------------------------------------------
@@ -511,6 +583,17 @@ class ReadCase(Case):
         r = host["recs"].view(READ_DT)
         return dict(status=r["status"].copy(), type=r["out_checksum_type"].copy(), value=r["out_checksum"].copy())
 
+    layouts = {"recs": READ_DT}
+
+    def output_mask(self, inp):
+        # hf3fs_crc_read_io's fields under "outputs" (hf3fs_crc.h:423-427); reserved0..2 and the
+        # struct's tail padding are not the call's.
+        return _masks(self.buffers(inp, 0), fields={"recs": (READ_DT, ("out_checksum", "out_checksum_type", "status"))})
+
+    def store(self, inp, host, ref):
+        r = host["recs"].view(READ_DT)
+        r["status"], r["out_checksum_type"], r["out_checksum"] = ref["status"], ref["type"], ref["value"]
+
 
 # ---- scrub ----------------------------------------------------------------------------------------
 def _scrub_restore(inp, rng):
@@ -601,6 +684,18 @@ class ScrubCase(Case):
     def extract(self, inp, host):
         r = host["recs"].view(SCRUB_DT)
         return dict(status=r["status"].copy(), computed=r["computed"].copy(), count=host["count"])
+
+    layouts = {"recs": SCRUB_DT}
+
+    def output_mask(self, inp):
+        # hf3fs_crc_scrub_io: computed and status are "out" (hf3fs_crc.h:499-500; computed is
+        # written for every record, "0 for NONE"); *d_mismatch_count is SET (hf3fs_crc.h:507).
+        return _masks(self.buffers(inp, 0), ("count",), {"recs": (SCRUB_DT, ("computed", "status"))})
+
+    def store(self, inp, host, ref):
+        r = host["recs"].view(SCRUB_DT)
+        r["status"], r["computed"] = ref["status"], ref["computed"]
+        host["count"][:] = ref["count"]
 
 
 # ---- serde frames ---------------------------------------------------------------------------------
@@ -721,6 +816,18 @@ class FramesCase(Case):
         f = host["frames"].view(FRAME_DT)
         return dict(status=f["status"].copy(), computed=f["computed"].copy(), count=host["count"])
 
+    layouts = {"frames": FRAME_DT}
+
+    def output_mask(self, inp):
+        # hf3fs_crc_frame: computed and status are "out" (hf3fs_crc.h:657-658); *d_mismatch_count
+        # is SET (hf3fs_crc.h:671).
+        return _masks(self.buffers(inp, 0), ("count",), {"frames": (FRAME_DT, ("computed", "status"))})
+
+    def store(self, inp, host, ref):
+        f = host["frames"].view(FRAME_DT)
+        f["status"], f["computed"] = ref["status"], ref["computed"]
+        host["count"][:] = ref["count"]
+
 
 # ---- file digest ----------------------------------------------------------------------------------
 def _m_digest_values(inp, rng):
@@ -794,6 +901,19 @@ class DigestCase(Case):
         return dict(status=o["status"].copy(), length=o["length"].copy(), type=np.where(ok, o["type"], 0).astype(np.uint8),
                     value=np.where(ok, o["value"], 0).astype(np.uint32))
 
+    layouts = {"blocks": BLOCK_DT, "out": FILE_DT}
+
+    def output_mask(self, inp):
+        # "the result (or the first error's status) goes to d_out[f]" (hf3fs_crc.h:468-469): d_out
+        # is an output array of whole hf3fs_crc_file_digest records, nothing in it is an input;
+        # d_blocks and d_file_off are const (hf3fs_crc.h:470-471, :480-482).
+        return _masks(self.buffers(inp, 0), ("out",))
+
+    def store(self, inp, host, ref):
+        o = host["out"].view(FILE_DT)
+        o[:] = np.zeros(1, dtype=FILE_DT)
+        o["status"], o["length"], o["type"], o["value"] = ref["status"], ref["length"], ref["type"], ref["value"]
+
 
 # ---- combine / serialize / finalize: no scratch, capture and replay only -------------------------
 def _m_scalar_values(inp, rng):
@@ -852,6 +972,16 @@ class ScalarCase(Case):
 
     def extract(self, inp, host):
         return {k: host[k] for k in dict(combine=("acc",), serialize=("out",), finalize=("values",))[self.name]}
+
+    def output_mask(self, inp):
+        # combine_batch updates d_acc in place, d_crc2 and d_len2 are const (hf3fs_crc.h:192-196);
+        # serialize_batch writes d_out = n x 6 bytes (hf3fs_crc.h:198-200); finalize_batch maps
+        # d_values in place (hf3fs_crc.h:203-205).
+        return _masks(self.buffers(inp, 0), dict(combine=("acc",), serialize=("out",), finalize=("values",))[self.name])
+
+    def store(self, inp, host, ref):
+        for k, v in ref.items():
+            host[k][:] = v
 
 
 CASES = {c.name: c for c in [

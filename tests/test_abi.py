@@ -144,6 +144,24 @@ def test_options_set_get_and_reject(hf):
     assert L.get_option("apply_grid") == "-1" and L.get_option("apply_piece_kib") == "8"
 
 
+def test_host_register_rejects_null_and_empty(hf):
+    """hf3fs_crc_host_register / _unregister: a null pointer, a zero length or a null result
+    pointer is kInvalidArg before any HIP call (so it is the answer on a machine without a GPU)."""
+    L = hf._lib
+    lib = L.load()
+    buf = ctypes.create_string_buffer(8192)
+    d = ctypes.c_void_p(0x1234)
+    assert lib.hf3fs_crc_host_register(None, 4096, ctypes.byref(d)) == hf.INVALID_ARG
+    assert lib.hf3fs_crc_host_register(ctypes.addressof(buf), 0, ctypes.byref(d)) == hf.INVALID_ARG
+    assert lib.hf3fs_crc_host_register(ctypes.addressof(buf), 4096, None) == hf.INVALID_ARG
+    assert d.value == 0x1234
+    assert lib.hf3fs_crc_host_unregister(None) == hf.INVALID_ARG
+    for args in ((0, 4096), (ctypes.addressof(buf), 0)):
+        with pytest.raises(hf.Hf3fsCrcError) as e:
+            L.host_register(*args)
+        assert e.value.code == hf.INVALID_ARG and "null argument" in str(e.value)
+
+
 def test_options_environment_read_once():
     """The environment is read at the first call only: a later change of HF3FS_CRC_* has no
     effect, and an invalid value or a retired switch is reported on stderr, not applied."""

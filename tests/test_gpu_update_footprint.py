@@ -37,24 +37,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _set_pipeline(opts, pipeline):
-    """The option sets of test_gpu_parity.py's _set_pipeline; "ticketed": the three-pass pipeline
-    with the ticketed apply on every call; "oneshot<K>": one-shot apply, K KiB pieces, every call."""
-    opts("update_pipeline", "fused" if pipeline == "fused" else "unfused")
-    if pipeline == "ticketed":
-        opts("apply_grid", 0)
-    if pipeline == "unfused_fine":
-        opts("apply_grid", 0)
-        opts("apply_pieces", 64)
-        opts("apply_min_kib", 1)
-    if pipeline == "oneshot_loop":
-        opts("apply_grid", 2)
-        opts("apply_piece_kib", 4)
-    if pipeline.startswith("oneshot") and pipeline != "oneshot_loop":
-        opts("apply_grid", 1)
-        opts("apply_piece_kib", int(pipeline[len("oneshot"):]))
-
-
 def _variants():
     """(pipeline, apply_nt, mode, checksum type): one entry per compiled copy variant and mode.
     Ticketed apply: apply_nt 0..7 (bit 0 / 1 non-temporal loads / stores, bit 2 the copy_range_hw
@@ -126,7 +108,7 @@ class GpuBackend:
 
 def _run(hf, orc, dev, opts, name, variant):
     pipeline, nt, mode, ctype = variant
-    _set_pipeline(opts, pipeline)
+    fp.set_pipeline(opts, pipeline)
     opts("apply_nt", nt)
     fp.run_scenario(_scenario(orc, name, ctype), GpuBackend(hf, dev, ctype, mode))
 

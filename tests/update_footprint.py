@@ -332,6 +332,26 @@ def run_scenario(scn, backend, rounds=None):
         check_round(scn, k, got[0], got[1], got[2], sent)
 
 
+# ---- the update pipelines a GPU backend can be run under -------------------------------------
+def set_pipeline(opts, pipeline):
+    """opts(name, value) sets a library switch (conftest's `opts`).  The option sets of
+    test_gpu_parity.py's _set_pipeline; "ticketed": the three-pass pipeline
+    with the ticketed apply on every call; "oneshot<K>": one-shot apply, K KiB pieces, every call."""
+    opts("update_pipeline", "fused" if pipeline == "fused" else "unfused")
+    if pipeline == "ticketed":
+        opts("apply_grid", 0)
+    if pipeline == "unfused_fine":
+        opts("apply_grid", 0)
+        opts("apply_pieces", 64)
+        opts("apply_min_kib", 1)
+    if pipeline == "oneshot_loop":
+        opts("apply_grid", 2)
+        opts("apply_piece_kib", 4)
+    if pipeline.startswith("oneshot") and pipeline != "oneshot_loop":
+        opts("apply_grid", 1)
+        opts("apply_piece_kib", int(pipeline[len("oneshot"):]))
+
+
 # ---- the cases ----------------------------------------------------------------------------------
 def _random_ios(rng, n_chunks, chunk_size, sizes, cks, pattern):
     """tests/test_gpu_parity.py's generator, unchanged."""
