@@ -21,4 +21,6 @@ from ._lib import (SYNC_CHAIN_VER_LOW, SYNC_CHAIN_WRITING, SYNC_CHAIN_WRITING_CH
                    SYNC_LOCAL_UNCOMMITTED, SYNC_MATCHED, SYNC_NONE, SYNC_REMOTE_CHAIN_VER_HIGH, SYNC_REMOTE_MISS,
                    SYNC_REMOTE_ONLY, SYNC_REMOTE_UNCOMMITTED, SyncMeta, sync_plan, sync_plan_scratch_bytes,
                    sync_scrub_fill)
+from ._lib import (UPDATE_COMMIT, VER_INFO_NAMES, VER_INFO_WORDS, update_ver_dtype, update_versioned,  # noqa: F401
+                   update_versioned_scratch_bytes)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

@@ -61,6 +61,25 @@ DIGEST_FILL_ZERO = 1  # hf3fs_crc_file_digest_batch_ex flags
 CKCASE_NONE, CKCASE_REUSE, CKCASE_COMBINE, CKCASE_RECOMPUTE = 1, 2, 3, 4
 
 
+UPDATE_COMMIT = 16  # a commit job of update_versioned (UpdateType::COMMIT)
+CHUNK_STATE_COMMIT, CHUNK_STATE_DIRTY, CHUNK_STATE_CLEAN = 0, 1, 2
+(CHUNK_NOT_CLEAN, CHUNK_STALE_UPDATE, CHUNK_MISSING_UPDATE, CHUNK_COMMITTED_UPDATE, CHUNK_ADVANCE_UPDATE,
+ CHUNK_SIZE_MISMATCH, CHUNK_STALE_COMMIT, CHAIN_VERSION_MISMATCH, CHUNK_VERSION_MISMATCH) = (
+    4005, 4006, 4007, 4008, 4012, 4015, 4023, 4081, 4082)
+VER_INFO_WORDS = 8
+VER_INFO_NAMES = ("chain_max", "not_applied", "updates", "commits", "refused", "fatal", "commit_dirty", "commit_stale")
+
+
+def update_ver_dtype():
+    """numpy dtype of hf3fs_crc_update_ver (include/hf3fs_crc.h): one 48-byte record per job."""
+    import numpy as np
+    return np.dtype([("io_ver", "<u4"), ("job_chain_ver", "<u4"), ("chain_ver", "<u4"), ("update_ver", "<u4"),
+                     ("commit_ver", "<u4"), ("meta_chunk_size", "<u4"), ("chunk_state", "u1"), ("recycle_state", "u1"),
+                     ("is_force", "u1"), ("reserved0", "u1"), ("out_chain_ver", "<u4"), ("out_update_ver", "<u4"),
+                     ("out_commit_ver", "<u4"), ("out_chunk_state", "u1"), ("out_recycle_state", "u1"),
+                     ("reserved1", "u1", (2,)), ("reserved2", "<u4")])
+
+
 class ReadIO(ctypes.Structure):
     """hf3fs_crc_read_io (include/hf3fs_crc.h): AioReadJob::setResult inputs/outputs."""
     _fields_ = [
@@ -256,6 +275,8 @@ SIGNATURES = {
     "hf3fs_crc_update_scratch_bytes": (ctypes.c_size_t, [_u64, _int]),
     "hf3fs_crc_update_ordered": (_int, [_u8, _vp, _u64, _u32, _int, _u32, _vp, _vp]),
     "hf3fs_crc_update_ordered_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int, _u32]),
+    "hf3fs_crc_update_versioned": (_int, [_u8, _vp, _vp, _u64, _u32, _int, _u32, _vp, _vp]),
+    "hf3fs_crc_update_versioned_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int, _u32]),
     "hf3fs_crc_update_cow_batch": (_int, [_u8, _vp, _vp, _u64, _u32, _int, _vp]),
     "hf3fs_crc_update_cow_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int]),
     "hf3fs_crc_pair_scratch_stats": (_int, [_vp, _vp, _vp]),
@@ -396,6 +417,19 @@ def update_ordered(ctype, ios, n, max_len, max_rounds, mode=MODE_REFERENCE, info
 def update_ordered_scratch_bytes(n, max_len, max_rounds, mode=MODE_REFERENCE):
     """Bytes of library-owned scratch one update_ordered of this shape takes (0: rejected arguments)."""
     return int(load().hf3fs_crc_update_ordered_scratch_bytes(n, max_len, mode, max_rounds))
+
+
+def update_versioned(ctype, ios, ver, n, max_len, max_rounds, mode=MODE_REFERENCE, info=None, stream=None):
+    """hf3fs_crc_update_versioned: update_ordered with the reference's version ladder and commit jobs.
+    ver: a device array of n hf3fs_crc_update_ver (update_ver_dtype()) parallel to ios, or None (the
+    call is then update_ordered); info: VER_INFO_WORDS device u32 words or None."""
+    return check(load().hf3fs_crc_update_versioned(ctype, _p(ios), _p(ver), n, max_len, mode, max_rounds, _p(info),
+                                                   _s(stream)))
+
+
+def update_versioned_scratch_bytes(n, max_len, max_rounds, mode=MODE_REFERENCE):
+    """Bytes of library-owned scratch one update_versioned with version records takes (0: rejected)."""
+    return int(load().hf3fs_crc_update_versioned_scratch_bytes(n, max_len, mode, max_rounds))
 
 
 def update_cow(ctype, ios, dst, n, max_len, mode=MODE_REFERENCE, stream=None):

@@ -31,6 +31,7 @@
 #include "sync_kernels.h"
 #include "update_kernels.h"
 #include "update_plan.h"  // kPlanRanges
+#include "version_kernels.h"
 
 static_assert(sizeof(hf3fs_crc_update_io) == 56, "hf3fs_crc_update_io ABI layout");
 static_assert(sizeof(hf3fs_crc_read_io) == 48, "hf3fs_crc_read_io ABI layout");
@@ -1098,6 +1099,59 @@ int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t 
     if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
   }
   HIP_OR_FAIL(launch_order_step(d_ios, n, max_rounds, max_rounds, os, d_info, s));
+  return HF3FS_CRC_OK;
+}
+
+// update_ordered with the version ladders (version_kernels.h).  Round 0 plans on the ordered
+// call's hint word: for a queue the ladders admit whole it IS that call's round 0.
+static size_t versioned_order_bytes(uint64_t n) { return (order_scratch_bytes(n) + 63) & ~size_t(63); }
+
+size_t hf3fs_crc_update_versioned_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds) {
+  const size_t ordered = hf3fs_crc_update_ordered_scratch_bytes(n, max_len, mode, max_rounds);
+  if (!ordered) return 0;
+  return ordered - order_scratch_bytes(n) + versioned_order_bytes(n) + version_scratch_bytes(n);
+}
+
+int hf3fs_crc_update_versioned(uint8_t type, hf3fs_crc_update_io* d_ios, hf3fs_crc_update_ver* d_ver, uint64_t n,
+                               uint32_t max_len, int mode, uint32_t max_rounds, uint32_t* d_info, void* stream) {
+  if (!d_ver) return hf3fs_crc_update_ordered(type, d_ios, n, max_len, mode, max_rounds, d_info, stream);
+  if (int rc = ordered_args(type, mode, max_rounds)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    if (d_info) HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_VER_INFO_WORDS, s));
+    return HF3FS_CRC_OK;
+  }
+  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  UpdatePlan first;
+  if (int rc = plan_update(c, kEntryOrdered, n, max_len, mode, nullptr, &s, &first)) return rc;
+  UpdatePlan later = first;  // (as in update_ordered: later rounds take the ticketed apply)
+  later.one_shot = false;
+  later.ptab_cap = 0;
+  later.hint = nullptr;
+  later.grid = (uint32_t)c->cus * 8;
+  const size_t pipe_bytes = ordered_pipeline_bytes(first, n), order_bytes = versioned_order_bytes(n);
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, pipe_bytes + order_bytes + version_scratch_bytes(n), &base)) return rc;
+  OrderScratch os;
+  VersionScratch vs;
+  order_scratch_carve((uint8_t*)base + pipe_bytes, n, &os);
+  version_scratch_carve((uint8_t*)base + pipe_bytes + order_bytes, n, &vs);
+  HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
+  for (uint32_t r = 0; r < max_rounds; ++r) {
+    HIP_OR_FAIL(launch_version_step(d_ios, d_ver, n, r, max_rounds, max_len, type, mode, os, vs, d_info, s));
+    if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
+  }
+  HIP_OR_FAIL(launch_version_step(d_ios, d_ver, n, max_rounds, max_rounds, max_len, type, mode, os, vs, d_info, s));
+  // The payloads of the jobs the version rungs refused: 4080 goes first (ChunkReplica.cc:193-207).
+  // Every other entry of the list is empty; with no such job the pass finds a length bound of 0.
+  const ListSource late{vs.vaddr, vs.vlen, nullptr, n, ~0u};
+  if (int rc = run_ranges_list(c, type == kTypeNone ? kTypeCrc32c : type, late, max_len, vs.vout, s, 0,
+                               os.ctl + kOrdVerMaxLen, nullptr, os.ctl + kOrdVerQueue))
+    return rc;
+  HIP_OR_FAIL(launch_version_settle(d_ios, n, max_rounds, os, vs, d_info, s));
   return HF3FS_CRC_OK;
 }
 

@@ -33,6 +33,8 @@ enum { HF3FS_CHECKSUM_NONE = 0, HF3FS_CHECKSUM_CRC32C = 1, HF3FS_CHECKSUM_CRC32 
 
 /* enum class UpdateType : uint8_t (src/fbs/storage/Common.h:51-57) */
 enum { HF3FS_UPDATE_WRITE = 1, HF3FS_UPDATE_TRUNCATE = 4, HF3FS_UPDATE_EXTEND = 8 };
+/* UpdateType::COMMIT (Common.h:57): a commit job of hf3fs_crc_update_versioned, valid in that call only */
+enum { HF3FS_UPDATE_COMMIT = 16 };
 
 /* Status codes: the reference's numeric codes (src/common/utils/StatusCodeDetails.h). */
 enum {
@@ -40,8 +42,17 @@ enum {
   HF3FS_CRC_INVALID_ARG = 3,                  /* StatusCode::kInvalidArg (:24) */
   HF3FS_CRC_INVALID_FORMAT = 33,              /* StatusCode::kInvalidFormat (:42) */
   HF3FS_CRC_SERDE_INSUFFICIENT_LENGTH = 40,   /* StatusCode::kSerdeInsufficientLength (:44) */
+  HF3FS_CRC_CHUNK_NOT_CLEAN = 4005,           /* StorageCode::kChunkNotClean (:155) */
+  HF3FS_CRC_CHUNK_STALE_UPDATE = 4006,        /* StorageCode::kChunkStaleUpdate (:156) */
+  HF3FS_CRC_CHUNK_MISSING_UPDATE = 4007,      /* StorageCode::kChunkMissingUpdate (:157) */
+  HF3FS_CRC_CHUNK_COMMITTED_UPDATE = 4008,    /* StorageCode::kChunkCommittedUpdate (:158) */
   HF3FS_CRC_CHUNK_READ_FAILED = 4010,         /* StorageCode::kChunkReadFailed (:160) */
+  HF3FS_CRC_CHUNK_ADVANCE_UPDATE = 4012,      /* StorageCode::kChunkAdvanceUpdate (:162) */
+  HF3FS_CRC_CHUNK_SIZE_MISMATCH = 4015,       /* StorageCode::kChunkSizeMismatch (:165) */
+  HF3FS_CRC_CHUNK_STALE_COMMIT = 4023,        /* StorageCode::kChunkStaleCommit (:172) */
   HF3FS_CRC_CHECKSUM_MISMATCH = 4080,         /* StorageCode::kChecksumMismatch (:186) */
+  HF3FS_CRC_CHAIN_VERSION_MISMATCH = 4081,    /* StorageCode::kChainVersionMismatch (:187) */
+  HF3FS_CRC_CHUNK_VERSION_MISMATCH = 4082,    /* StorageCode::kChunkVersionMismatch (:188) */
   HF3FS_CRC_CHUNK_NOT_FOUND = 7007,           /* StorageClientCode::kChunkNotFound (:228) */
   HF3FS_CRC_CLIENT_CHECKSUM_MISMATCH = 7015,  /* StorageClientCode::kChecksumMismatch (:236) */
   HF3FS_CRC_DEVICE_ERROR = 9001,              /* HIP runtime failure, or an update IO whose verify the
@@ -360,6 +371,90 @@ int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io *d_ios, uint64_t 
  * call of the largest (n, max_len, max_rounds) of a mode, no later call on the pair grows the
  * buffer.  0 for arguments the call would reject. */
 size_t hf3fs_crc_update_ordered_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds);
+
+/* The version state of one job of hf3fs_crc_update_versioned, parallel to its hf3fs_crc_update_io:
+ * what UpdateWorker knows from the UpdateJob (io_ver, job_chain_ver, is_force) and the chunk's
+ * ChunkMetadata (Common.h:652-677) before the job, and the metadata the job leaves. */
+typedef struct hf3fs_crc_update_ver {
+  uint32_t io_ver;          /* UpdateIO.updateVer (0: this replica assigns) / CommitIO.commitVer */
+  uint32_t job_chain_ver;   /* job.commitChainVer() */
+  /* ChunkMetadata before the job: read from the chunk's first job, OVERWRITTEN for every later one */
+  uint32_t chain_ver, update_ver, commit_ver;
+  uint32_t meta_chunk_size; /* meta.innerFileId.chunkSize */
+  uint8_t chunk_state;      /* HF3FS_CHUNK_STATE_*: COMMIT 0, DIRTY 1, CLEAN 2 */
+  uint8_t recycle_state;    /* 0 = NORMAL */
+  uint8_t is_force;         /* CommitIO.isForce */
+  uint8_t reserved0;
+  /* ChunkMetadata after the job (== before, when the job fails) */
+  uint32_t out_chain_ver, out_update_ver, out_commit_ver;
+  uint8_t out_chunk_state, out_recycle_state, reserved1[2];
+  uint32_t reserved2;
+} hf3fs_crc_update_ver;
+
+/* enum class ChunkState : uint8_t (Common.h) */
+enum { HF3FS_CHUNK_STATE_COMMIT = 0, HF3FS_CHUNK_STATE_DIRTY = 1, HF3FS_CHUNK_STATE_CLEAN = 2 };
+
+/* Words of hf3fs_crc_update_versioned's d_info */
+enum {
+  HF3FS_VER_INFO_CHAIN_MAX = 0,     /* longest chain of the batch (uncapped) */
+  HF3FS_VER_INFO_NOT_APPLIED = 1,   /* NOT_APPLIED jobs */
+  HF3FS_VER_INFO_UPDATES = 2,       /* applied updates */
+  HF3FS_VER_INFO_COMMITS = 3,       /* applied commits */
+  HF3FS_VER_INFO_REFUSED = 4,       /* jobs with any other non-zero status */
+  HF3FS_VER_INFO_FATAL = 5,         /* the reference's fatal events among them (4080, 4081, 4082) */
+  HF3FS_VER_INFO_COMMIT_DIRTY = 6,  /* commits refused DIRTY (storage.commit.dirty) */
+  HF3FS_VER_INFO_COMMIT_STALE = 7,  /* stale commits (storage.commit.stale) */
+  HF3FS_VER_INFO_WORDS = 8
+};
+
+/* hf3fs_crc_update_ordered with the part of ChunkReplica::update that decides whether a job may run
+ * at all: the updateVer / commitVer / chainVer / ChunkState ladder (ChunkReplica.cc:171-191,211-245)
+ * and ChunkReplica::commit (:397-467) as a job of the same queue.  n jobs in ARRIVAL ORDER; job i
+ * is d_ios[i] with d_ver[i].  Identity, the hand-over of {size, checksum type, checksum value},
+ * max_rounds in 1..64, NOT_APPLIED, stream, capture, scratch and poison rules are update_ordered's.
+ * With d_ver == NULL the call IS hf3fs_crc_update_ordered, byte for byte, d_info's two words
+ * included (HF3FS_UPDATE_COMMIT is then an unknown update type, kInvalidArg for that IO).
+ * State hand-over: the chunk's first job takes chain_ver, update_ver, commit_ver, meta_chunk_size,
+ * chunk_state and recycle_state from its own record; for every later job these six are OVERWRITTEN
+ * with what its predecessor left.  A chunk without metadata (kChunkMetadataNotFound, :154-164) is
+ * described by the caller: size 0, versions 0, chunk_state CLEAN, chain_ver = job_chain_ver,
+ * meta_chunk_size = max_len.  out_* are the metadata after the job; the IOResult version fields
+ * the reference returns (updateVer, commitVer, commitChainVer) are out_* on success and the
+ * before-state on failure, which out_* then repeat.
+ * An update job (WRITE / TRUNCATE / EXTEND, replica IOs) gets the first status that holds:
+ *   1. kInvalidArg: every one the plain call gives for the record; HF3FS_UPDATE_FLAG_ENGINE (the
+ *      engine's ladder, engine.rs:340-365, is another one); any other update type (REMOVE).
+ *   2. 4015 meta_chunk_size != max_len (:176).
+ *   3. 4005 chunk_state DIRTY and the IO is not HF3FS_UPDATE_FLAG_SYNCING (:181).
+ *   4. 4081 job_chain_ver < chain_ver and chunk_state COMMIT (:186).
+ *   5. 4080 from the payload verify (:193-207); the self-check's 9001 stands here too.
+ *   6. Syncing: update_ver = io_ver, commit_ver = io_ver - 1, recycle_state = 0.
+ *      io_ver > 0: 4008 if io_ver <= commit_ver; 4006 if io_ver <= update_ver; 4007 if io_ver >
+ *      update_ver + 1; else update_ver = io_ver.
+ *      io_ver == 0: 4012 if update_ver + 1 > commit_ver + 1; else update_ver += 1.
+ *   7. applied exactly as update_ordered applies it; chunk_state CLEAN, chain_ver = job_chain_ver.
+ * A payload mismatch wins over a refusal at rung 6; a job refused at rungs 1-4 is never hashed.
+ * A commit job (update_type HF3FS_UPDATE_COMMIT; payload, offset, length are ignored) takes one
+ * round and touches no byte: kInvalidArg on a chunk with recycle_state != 0 (that commit is
+ * store.remove, left to the host) or with the ENGINE flag; 4081 if job_chain_ver < chain_ver; 4082
+ * if io_ver > update_ver; is_force: CLEAN, commit_ver = io_ver; else DIRTY -> 4005; else
+ * commit_ver < io_ver sets it; else 4023.  Then commit_ver == update_ver makes the chunk COMMIT with
+ * chain_ver = job_chain_ver.  Its out_size / out_checksum{,_type} repeat the chunk's, case 0.
+ * Every failure leaves bytes, size, checksum and version state untouched; the chunk's next job
+ * starts from them.  For a refused job the output fields of d_ios are those of an IO that failed
+ * its verify (the input state repeated, case 0) with the refusal in status.  Version arithmetic is
+ * uint32_t (ChunkVer).  A NOT_APPLIED job carries the chunk's state after its last applied job in
+ * the input and the out_* fields of both records.
+ * d_info may be NULL; else HF3FS_VER_INFO_WORDS device words SET by the call.
+ * Cost on top of update_ordered: the step between rounds reads and writes the 48-byte records and
+ * runs the ladders; after the last round one hashing pass verifies the payloads of the jobs refused
+ * at rung 6 (nothing to hash when there is none) and one kernel settles them and counts d_info.
+ * Nothing is decided on the host or read back: a replayed graph re-plans from the records. */
+int hf3fs_crc_update_versioned(uint8_t type, hf3fs_crc_update_io *d_ios, hf3fs_crc_update_ver *d_ver, uint64_t n,
+                               uint32_t max_len, int mode, uint32_t max_rounds, uint32_t *d_info, void *stream);
+/* Bytes of scratch one such call with version records takes (update_ordered's rule: after one call
+ * of the largest shape nothing grows).  0 for arguments the call would reject. */
+size_t hf3fs_crc_update_versioned_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds);
 /* hf3fs_crc_update_batch with a destination per IO: Chunk::copy_on_write (chunk_engine/src/alloc/
  * chunk.rs:89-174), which writes the new version of a chunk into a newly allocated one and leaves
  * the committed version readable.  d_dst is a device array of n destination addresses, or NULL.
