@@ -23,4 +23,6 @@ from ._lib import (SYNC_CHAIN_VER_LOW, SYNC_CHAIN_WRITING, SYNC_CHAIN_WRITING_CH
                    sync_scrub_fill)
 from ._lib import (UPDATE_COMMIT, VER_INFO_NAMES, VER_INFO_WORDS, update_ver_dtype, update_versioned,  # noqa: F401
                    update_versioned_scratch_bytes)
+from ._lib import (ENGINE_INFO_NAMES, ENGINE_INFO_WORDS, engine_job_dtype, update_engine,  # noqa: F401
+                   update_engine_scratch_bytes)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

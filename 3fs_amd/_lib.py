@@ -61,7 +61,7 @@ DIGEST_FILL_ZERO = 1  # hf3fs_crc_file_digest_batch_ex flags
 CKCASE_NONE, CKCASE_REUSE, CKCASE_COMBINE, CKCASE_RECOMPUTE = 1, 2, 3, 4
 
 
-UPDATE_COMMIT = 16  # a commit job of update_versioned (UpdateType::COMMIT)
+UPDATE_COMMIT = 16  # a commit job of update_versioned / update_engine (UpdateType::COMMIT)
 CHUNK_STATE_COMMIT, CHUNK_STATE_DIRTY, CHUNK_STATE_CLEAN = 0, 1, 2
 (CHUNK_NOT_CLEAN, CHUNK_STALE_UPDATE, CHUNK_MISSING_UPDATE, CHUNK_COMMITTED_UPDATE, CHUNK_ADVANCE_UPDATE,
  CHUNK_SIZE_MISMATCH, CHUNK_STALE_COMMIT, CHAIN_VERSION_MISMATCH, CHUNK_VERSION_MISMATCH) = (
@@ -78,6 +78,22 @@ def update_ver_dtype():
                      ("is_force", "u1"), ("reserved0", "u1"), ("out_chain_ver", "<u4"), ("out_update_ver", "<u4"),
                      ("out_commit_ver", "<u4"), ("out_chunk_state", "u1"), ("out_recycle_state", "u1"),
                      ("reserved1", "u1", (2,)), ("reserved2", "<u4")])
+
+
+ENGINE_DETAIL_NONE, ENGINE_DETAIL_RECORD, ENGINE_DETAIL_IN_WRITING, ENGINE_DETAIL_NO_DST, ENGINE_DETAIL_NO_WRITING = range(5)
+ENGINE_INFO_WORDS = 8
+ENGINE_INFO_NAMES = ("chain_max", "not_applied", "updates", "commits", "refused", "cow", "in_place", "in_writing")
+
+
+def engine_job_dtype():
+    """numpy dtype of hf3fs_crc_engine_job (include/hf3fs_crc.h): one 104-byte record per job."""
+    import numpy as np
+    return np.dtype([("dst", "<u8"), ("addr", "<u8"), ("w_addr", "<u8"), ("out_addr", "<u8"), ("out_w_addr", "<u8"),
+                     ("io_ver", "<u4"), ("job_chain_ver", "<u4"), ("chain_ver", "<u4"), ("chunk_ver", "<u4"),
+                     ("w_len", "<u4"), ("w_checksum", "<u4"), ("w_chain_ver", "<u4"), ("w_chunk_ver", "<u4"),
+                     ("out_chain_ver", "<u4"), ("out_chunk_ver", "<u4"), ("out_w_len", "<u4"),
+                     ("out_w_checksum", "<u4"), ("out_w_chain_ver", "<u4"), ("out_w_chunk_ver", "<u4"),
+                     ("out_cow", "u1"), ("detail", "u1"), ("reserved", "u1", (6,))])
 
 
 class ReadIO(ctypes.Structure):
@@ -277,6 +293,8 @@ SIGNATURES = {
     "hf3fs_crc_update_ordered_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int, _u32]),
     "hf3fs_crc_update_versioned": (_int, [_u8, _vp, _vp, _u64, _u32, _int, _u32, _vp, _vp]),
     "hf3fs_crc_update_versioned_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int, _u32]),
+    "hf3fs_crc_update_engine": (_int, [_u8, _vp, _vp, _u64, _u32, _int, _u32, _vp, _vp]),
+    "hf3fs_crc_update_engine_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int, _u32]),
     "hf3fs_crc_update_cow_batch": (_int, [_u8, _vp, _vp, _u64, _u32, _int, _vp]),
     "hf3fs_crc_update_cow_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int]),
     "hf3fs_crc_pair_scratch_stats": (_int, [_vp, _vp, _vp]),
@@ -430,6 +448,19 @@ def update_versioned(ctype, ios, ver, n, max_len, max_rounds, mode=MODE_REFERENC
 def update_versioned_scratch_bytes(n, max_len, max_rounds, mode=MODE_REFERENCE):
     """Bytes of library-owned scratch one update_versioned with version records takes (0: rejected)."""
     return int(load().hf3fs_crc_update_versioned_scratch_bytes(n, max_len, mode, max_rounds))
+
+
+def update_engine(ctype, ios, jobs, n, max_len, max_rounds, mode=MODE_REFERENCE, info=None, stream=None):
+    """hf3fs_crc_update_engine: a chunk-engine target's queue of update and commit jobs in arrival
+    order.  jobs: a device array of n hf3fs_crc_engine_job (engine_job_dtype()) parallel to ios;
+    info: ENGINE_INFO_WORDS device u32 words or None."""
+    return check(load().hf3fs_crc_update_engine(ctype, _p(ios), _p(jobs), n, max_len, mode, max_rounds, _p(info),
+                                                _s(stream)))
+
+
+def update_engine_scratch_bytes(n, max_len, max_rounds, mode=MODE_REFERENCE):
+    """Bytes of library-owned scratch one update_engine of this shape takes (0: rejected arguments)."""
+    return int(load().hf3fs_crc_update_engine_scratch_bytes(n, max_len, mode, max_rounds))
 
 
 def update_cow(ctype, ios, dst, n, max_len, mode=MODE_REFERENCE, stream=None):

@@ -25,6 +25,7 @@
 #include "frame_kernels.h"
 #include "crc_kernels.h"
 #include "digest_kernels.h"
+#include "engine_kernels.h"
 #include "internal.h"
 #include "options.h"
 #include "order_kernels.h"
@@ -42,6 +43,8 @@ static_assert(sizeof(hf3fs_crc_sync_meta) == 48, "hf3fs_crc_sync_meta ABI layout
 static_assert(sizeof(hf3fs_crc_frame) == 24, "hf3fs_crc_frame ABI layout");
 static_assert(sizeof(hf3fs_crc_engine_meta) == 120, "hf3fs_crc_engine_meta ABI layout");
 static_assert(sizeof(hf3fs_crc_anomaly) == 72, "hf3fs_crc_anomaly ABI layout");
+static_assert(sizeof(hf3fs_crc_engine_job) == 104 && alignof(hf3fs_crc_engine_job) == 8,
+              "hf3fs_crc_engine_job ABI layout");
 
 using namespace hf3fs_crc;
 
@@ -81,9 +84,10 @@ struct PairState {
   Scratch call;                 // scratch of update / record / frame / digest batches
   Scratch balance;              // byte-balance region of whole-range launches (bal_words words)
   uint32_t* counter = nullptr;  // ticket counter: a 16 B slot of a shared slab, not owned
-  uint32_t hint[3] = {kNoHint, kNoHint, kNoHint};  // slots of the one-shot apply's pinned hint words:
-                                                   // [0] update_batch, [1] round 0 of update_ordered,
-                                                   // [2] update_cow_batch
+  uint32_t hint[4] = {kNoHint, kNoHint, kNoHint, kNoHint};  // slots of the one-shot apply's pinned hint
+                                                            // words: [0] update_batch, [1] round 0 of
+                                                            // update_ordered, [2] update_cow_batch,
+                                                            // [3] round 0 of update_engine
   Side side;
 };
 
@@ -852,7 +856,7 @@ size_t hf3fs_crc_update_scratch_bytes(uint64_t n, int mode) {
 // when no call has counted pieces yet (option apply_grid) or the piece table would be too large.
 // The entry point is also the index of the pair's hint word: what one entry point counts never
 // sizes the grid of another on the same pair.
-enum UpdateEntry { kEntryBatch = 0, kEntryOrdered = 1, kEntryCow = 2 };  // ordered: its round 0
+enum UpdateEntry { kEntryBatch = 0, kEntryOrdered = 1, kEntryCow = 2, kEntryEngine = 3 };  // ordered, engine: round 0
 struct UpdatePlan {
   bool unfused = false;
   uint32_t pieces = 0, piece_min = 0, rep = 1, nw = 0;
@@ -887,7 +891,7 @@ static uint32_t hinted_grid(uint64_t h, uint64_t n, uint64_t cap) {
 // to tickets.
 static int plan_update(Context* c, UpdateEntry entry, uint64_t n, uint32_t max_len, int mode, const uint64_t* d_dst,
                        const hipStream_t* s, UpdatePlan* p) {
-  const bool cow = entry == kEntryCow;
+  const bool cow = entry == kEntryCow || entry == kEntryEngine;  // (every round of update_engine is a COW batch)
   const int apply_grid = options().apply_grid.load();
   update_pipeline(mode, &p->unfused, &p->pieces, &p->piece_min);
   if (cow) {
@@ -1152,6 +1156,71 @@ int hf3fs_crc_update_versioned(uint8_t type, hf3fs_crc_update_io* d_ios, hf3fs_c
                                os.ctl + kOrdVerMaxLen, nullptr, os.ctl + kOrdVerQueue))
     return rc;
   HIP_OR_FAIL(launch_version_settle(d_ios, n, max_rounds, os, vs, d_info, s));
+  return HF3FS_CRC_OK;
+}
+
+// The chunk engine's queue (engine_kernels.h): the ordered call's planner, the engine's state
+// machine between rounds, and every round a copy-on-write batch over the step's destination array.
+// Every round takes the one-shot apply -- the copy-on-write pipeline has no ticketed form, and its
+// kernel loops when the grid is short; round 0 plans on the call's own hint word and leaves its
+// piece count there, the later rounds (which shrink fast) run on round 0's grid and leave none.
+static int engine_args(uint8_t type, int mode, uint32_t max_rounds) {
+  if (int rc = ordered_args(type, mode, max_rounds)) return rc;
+  if (type != kTypeCrc32c)
+    return fail(HF3FS_CRC_INVALID_ARG, "the chunk engine's checksum type is CRC32C, not %u", type);
+  return HF3FS_CRC_OK;
+}
+static size_t engine_pipeline_bytes(const UpdatePlan& p, uint64_t n) {
+  return (update_scratch_bytes(n, p.records, p.nw, p.ptab_cap) + 63) & ~size_t(63);
+}
+
+size_t hf3fs_crc_update_engine_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds) {
+  if (engine_args(kTypeCrc32c, mode, max_rounds) || n == 0 || n > kOrderedMaxIos) return 0;
+  Context* c = nullptr;
+  if (get_context(&c)) return 0;
+  UpdatePlan p;
+  if (plan_update(c, kEntryEngine, n, max_len, mode, nullptr, nullptr, &p)) return 0;
+  return engine_pipeline_bytes(p, n) + versioned_order_bytes(n) + engine_scratch_bytes(n);
+}
+
+int hf3fs_crc_update_engine(uint8_t type, hf3fs_crc_update_io* d_ios, hf3fs_crc_engine_job* d_jobs, uint64_t n,
+                            uint32_t max_len, int mode, uint32_t max_rounds, uint32_t* d_info, void* stream) {
+  if (int rc = engine_args(type, mode, max_rounds)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    if (d_info) HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_ENGINE_INFO_WORDS, s));
+    return HF3FS_CRC_OK;
+  }
+  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  if (!d_jobs) return fail(HF3FS_CRC_INVALID_ARG, "null jobs");
+  if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  const size_t order_bytes = versioned_order_bytes(n);
+  UpdatePlan first;
+  if (int rc = plan_update(c, kEntryEngine, n, max_len, mode, nullptr, &s, &first)) return rc;
+  const size_t pipe_bytes = engine_pipeline_bytes(first, n);
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, pipe_bytes + order_bytes + engine_scratch_bytes(n), &base)) return rc;
+  OrderScratch os;
+  EngineScratch es;
+  order_scratch_carve((uint8_t*)base + pipe_bytes, n, &os);
+  engine_scratch_carve((uint8_t*)base + pipe_bytes + order_bytes, n, &es);
+  first.dst = es.rdst;
+  UpdatePlan later = first;
+  later.hint = nullptr;
+  HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
+  for (uint32_t r = 0; r < max_rounds; ++r) {
+    HIP_OR_FAIL(launch_engine_step(d_ios, d_jobs, n, r, max_rounds, max_len, mode, os, es, d_info, s));
+    if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
+  }
+  HIP_OR_FAIL(launch_engine_step(d_ios, d_jobs, n, max_rounds, max_rounds, max_len, mode, os, es, d_info, s));
+  // The payloads of the jobs refused after the verify's place: 4080 goes first (engine.rs:297-311).
+  const ListSource late{es.v.vaddr, es.v.vlen, nullptr, n, ~0u};
+  if (int rc = run_ranges_list(c, kTypeCrc32c, late, max_len, es.v.vout, s, 0, os.ctl + kOrdVerMaxLen, nullptr,
+                               os.ctl + kOrdVerQueue))
+    return rc;
+  HIP_OR_FAIL(launch_engine_settle(d_ios, d_jobs, n, max_rounds, os, es, d_info, s));
   return HF3FS_CRC_OK;
 }
 

@@ -33,7 +33,8 @@ enum { HF3FS_CHECKSUM_NONE = 0, HF3FS_CHECKSUM_CRC32C = 1, HF3FS_CHECKSUM_CRC32 
 
 /* enum class UpdateType : uint8_t (src/fbs/storage/Common.h:51-57) */
 enum { HF3FS_UPDATE_WRITE = 1, HF3FS_UPDATE_TRUNCATE = 4, HF3FS_UPDATE_EXTEND = 8 };
-/* UpdateType::COMMIT (Common.h:57): a commit job of hf3fs_crc_update_versioned, valid in that call only */
+/* UpdateType::COMMIT (Common.h:57): a commit job of hf3fs_crc_update_versioned and
+ * hf3fs_crc_update_engine, valid in those calls only */
 enum { HF3FS_UPDATE_COMMIT = 16 };
 
 /* Status codes: the reference's numeric codes (src/common/utils/StatusCodeDetails.h). */
@@ -455,6 +456,114 @@ int hf3fs_crc_update_versioned(uint8_t type, hf3fs_crc_update_io *d_ios, hf3fs_c
 /* Bytes of scratch one such call with version records takes (update_ordered's rule: after one call
  * of the largest shape nothing grows).  0 for arguments the call would reject. */
 size_t hf3fs_crc_update_versioned_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds);
+
+/* The engine state of one job of hf3fs_crc_update_engine, parallel to its hf3fs_crc_update_io: what
+ * ChunkEngine::update / ::commit take from the UpdateJob (ChunkEngine.cc:39-40,96), the chunk's
+ * committed ChunkMeta and writing-list entry before the job, and what the job leaves.  The committed
+ * len and checksum are chunk_size / chunk_checksum_type / chunk_checksum of the IO record. */
+typedef struct hf3fs_crc_engine_job {
+  uint64_t dst;             /* a fresh allocation (capacity >= max_len) the job may copy_on_write into; 0 = none */
+  /* engine state before the job: read from the chunk's first job, OVERWRITTEN for every later one */
+  uint64_t addr;            /* device address of the committed version */
+  uint64_t w_addr;          /* device address of the writing version; 0 = no live holder */
+  /* engine state after the job (== before, when the job fails) */
+  uint64_t out_addr;
+  uint64_t out_w_addr;
+  uint32_t io_ver;          /* UpdateReq.update_ver (0: the engine assigns chunk_ver + 1) */
+  uint32_t job_chain_ver;   /* job.commitChainVer() */
+  uint32_t chain_ver, chunk_ver;                              /* before: committed ChunkMeta */
+  uint32_t w_len, w_checksum, w_chain_ver, w_chunk_ver;       /* before: the writing version (checksum raw) */
+  uint32_t out_chain_ver, out_chunk_ver;                      /* after: committed */
+  uint32_t out_w_len, out_w_checksum, out_w_chain_ver, out_w_chunk_ver;  /* after: writing */
+  uint8_t out_cow;          /* 1: the job wrote into dst */
+  uint8_t detail;           /* HF3FS_ENGINE_DETAIL_*: why status is kInvalidArg */
+  uint8_t reserved[6];
+} hf3fs_crc_engine_job;
+
+/* hf3fs_crc_engine_job.detail */
+enum {
+  HF3FS_ENGINE_DETAIL_NONE = 0,
+  HF3FS_ENGINE_DETAIL_RECORD = 1,      /* malformed record, no ENGINE flag, or an update type the call does not take */
+  HF3FS_ENGINE_DETAIL_IN_WRITING = 2,  /* the chunk has a live writing version (engine.rs:441-447) */
+  HF3FS_ENGINE_DETAIL_NO_DST = 3,      /* copy-on-write needed and dst == 0 */
+  HF3FS_ENGINE_DETAIL_NO_WRITING = 4   /* a commit without a writing version */
+};
+
+/* Words of hf3fs_crc_update_engine's d_info */
+enum {
+  HF3FS_ENGINE_INFO_CHAIN_MAX = 0,    /* longest chain of the batch (uncapped) */
+  HF3FS_ENGINE_INFO_NOT_APPLIED = 1,  /* NOT_APPLIED jobs */
+  HF3FS_ENGINE_INFO_UPDATES = 2,      /* applied updates */
+  HF3FS_ENGINE_INFO_COMMITS = 3,      /* applied commits */
+  HF3FS_ENGINE_INFO_REFUSED = 4,      /* jobs with any other non-zero status */
+  HF3FS_ENGINE_INFO_COW = 5,          /* applied updates that copied on write (copy_on_write_times) */
+  HF3FS_ENGINE_INFO_IN_PLACE = 6,     /* applied updates written in place (safe_write) */
+  HF3FS_ENGINE_INFO_IN_WRITING = 7,   /* updates refused because the chunk was in writing */
+  HF3FS_ENGINE_INFO_WORDS = 8
+};
+
+/* The queue of a chunk-engine target in ARRIVAL ORDER: ChunkEngine::update (ChunkEngine.cc:15-80)
+ * over Engine::update_chunk (chunk_engine/src/core/engine.rs:288-468) and ChunkEngine::commit
+ * (ChunkEngine.cc:82-110, engine.rs:470-507) as jobs of one call, with nothing decided on the host:
+ * the engine's version checks, the writing list, copy_on_write or safe_write chosen from the state
+ * each job actually meets, and the committed address moving to the destination at commit.  Job i is
+ * d_ios[i] with d_jobs[i].  max_rounds in 1..64, HF3FS_CRC_NOT_APPLIED, stream, capture, scratch and
+ * poison rules are hf3fs_crc_update_versioned's.  Argument errors (before any device is touched):
+ * those of update_versioned; type must be HF3FS_CHECKSUM_CRC32C (the engine knows no other);
+ * d_jobs == NULL with n > 0; a batch whose piece table would pass 1 GiB (as update_cow_batch).
+ * Identity: two jobs address the same chunk iff their d_ios[i].chunk are equal.  In this call
+ * `chunk` is a key only and is never dereferenced (normally the committed address at queue time);
+ * the bytes are found through `addr`.
+ * State hand-over: the chunk's first job takes addr, chain_ver, chunk_ver, the five w_* fields and
+ * the IO record's chunk_size / chunk_checksum_type / chunk_checksum from its own records; for every
+ * later job they are OVERWRITTEN with what its predecessor left.  Unlike update_ordered the next job
+ * starts from the COMMITTED {size, checksum}, which an update does not change, and with the writing
+ * fields set.  A chunk the engine does not know (engine.rs:327-337) is described by the caller:
+ * size 0, chunk_ver 0, chain_ver = job_chain_ver, addr = the allocation the engine would make (:405).
+ * An update job (WRITE / TRUNCATE / EXTEND with HF3FS_UPDATE_FLAG_ENGINE) gets the first that holds:
+ *   1. kInvalidArg, detail 1: every kInvalidArg the plain call gives for the record; a record
+ *      without the ENGINE flag; any other update type (REMOVE stays on the host).
+ *   2. 4080 from the payload verify (engine.rs:297-311); the self-check's 9001 stands here too.  It
+ *      precedes every version rung: a job refused at 3-6 still has its payload hashed, 4080 wins.
+ *   3. 4081 if job_chain_ver < chain_ver (:340).
+ *   4. Not syncing and io_ver > 0: 4008 if io_ver <= chunk_ver; 4007 if io_ver > chunk_ver + 1.
+ *   5. kInvalidArg, detail 3, if the job must copy on write and dst == 0.
+ *   6. kInvalidArg, detail 2, if w_addr != 0 (:441-447).
+ *   7. Applied.  The new version is io_ver (syncing, or io_ver > 0), else chunk_ver + 1, in uint32_t
+ *      arithmetic (the engine's release build wraps).  Copy on write iff syncing, or a WRITE with
+ *      length > 0 && offset < chunk_size (:377-380; the capacity clause never holds: capacity is
+ *      taken as max_len): the record is applied exactly as hf3fs_crc_update_cow_batch applies it
+ *      from addr into dst, out_cow = 1.  Otherwise it is applied in place at addr exactly as
+ *      hf3fs_crc_update_batch does (safe_write) and dst is not touched.  Afterwards the writing
+ *      version is {out_cow ? dst : addr, out_size, out_checksum, job_chain_ver, new version}; the
+ *      committed state is unchanged.  out_size, out_checksum and checksum_case of the IO record are
+ *      the pipeline's: what ChunkEngine::update returns (:61-66).
+ * A commit job (update_type HF3FS_UPDATE_COMMIT; payload, offset, length, io_ver ignored) takes one
+ * round and touches no byte: kInvalidArg, detail 4, if w_addr == 0; else the committed state becomes
+ * the writing version with chain_ver = job_chain_ver and the writing fields are cleared: out_addr =
+ * w_addr, out_size / out_checksum repeat the new committed state (type CRC32C), checksum_case 0.
+ * The caller recycles the old allocation when out_addr != addr; a dst whose job came back with
+ * out_cow == 0 goes back to the allocator.
+ * Every failure leaves bytes, committed and writing state untouched; out_* repeat the before-state
+ * and the IO record's outputs are those of an IO that failed its verify (input state repeated,
+ * case 0).  A NOT_APPLIED job carries the chunk's state after its last applied job in the input and
+ * out_* fields of both records.
+ * Two deliberate differences from the reference: on 4080 its IOResult carries zero versions
+ * (engine.rs:303 returns before :322), this call repeats the before-state like every other refusal;
+ * and a job refused "in writing" has, in the reference, already written its bytes (a safe_write
+ * scribbles past the committed length at the shared position) -- here a refused job writes nothing.
+ * d_info may be NULL; else HF3FS_ENGINE_INFO_WORDS device words SET by the call.
+ * Aliasing: every dst has capacity >= max_len and overlaps no chunk, payload, record or other dst
+ * of the batch; anything else is undefined, as for update_cow_batch.
+ * Pipeline: every round is update_cow_batch's (three passes, one-shot apply) with a per-round
+ * destination array; the grid hint word is the call's own, so update_batch, update_ordered,
+ * update_versioned and update_cow_batch calls on the same pair plan as if no engine call had run. */
+int hf3fs_crc_update_engine(uint8_t type, hf3fs_crc_update_io *d_ios, hf3fs_crc_engine_job *d_jobs, uint64_t n,
+                            uint32_t max_len, int mode, uint32_t max_rounds, uint32_t *d_info, void *stream);
+/* Bytes of scratch one such call takes (after one call of the largest (n, max_len, max_rounds)
+ * nothing grows).  0 for arguments the call would reject. */
+size_t hf3fs_crc_update_engine_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds);
+
 /* hf3fs_crc_update_batch with a destination per IO: Chunk::copy_on_write (chunk_engine/src/alloc/
  * chunk.rs:89-174), which writes the new version of a chunk into a newly allocated one and leaves
  * the committed version readable.  d_dst is a device array of n destination addresses, or NULL.
