@@ -25,4 +25,6 @@ from ._lib import (UPDATE_COMMIT, VER_INFO_NAMES, VER_INFO_WORDS, update_ver_dty
                    update_versioned_scratch_bytes)
 from ._lib import (ENGINE_INFO_NAMES, ENGINE_INFO_WORDS, engine_job_dtype, update_engine,  # noqa: F401
                    update_engine_scratch_bytes)
+from ._lib import (MD5_FINAL, MD5_INIT, md5_batch, md5_hex, md5_scratch_bytes, md5_seg_dtype,  # noqa: F401
+                   md5_state_dtype)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

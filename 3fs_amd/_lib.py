@@ -301,6 +301,9 @@ SIGNATURES = {
     "hf3fs_crc_read_result_batch": (_int, [_u8, _vp, _u64, _u32, _vp]),
     "hf3fs_crc_file_digest_batch": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "hf3fs_crc_file_digest_batch_ex": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
+    "hf3fs_crc_md5_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp]),
+    "hf3fs_crc_md5_scratch_bytes": (ctypes.c_size_t, [_u64]),
+    "hf3fs_crc_md5_hex": (_u32, [_vp, _vp]),
     "hf3fs_crc_create_host": (_int, [_u8, _vp, _vp, _vp, _vp, _u64]),
     "hf3fs_crc_fill_synth": (_int, [_vp, _u64, _u64, _u64, _u64, _u64, _vp]),
     "hf3fs_crc_scrub_batch": (_int, [_u8, _vp, _u64, _u32, _vp, _vp]),
@@ -546,6 +549,45 @@ def file_digest_batch(blocks, file_off, out, n_files, max_blocks, stream=None, f
     the admin command without --fill-zero (first missing / short block is the status)."""
     return check(load().hf3fs_crc_file_digest_batch_ex(_p(blocks), _p(file_off), _p(out), n_files, max_blocks,
                                                        DIGEST_FILL_ZERO if fill_zero else 0, _s(stream)))
+
+
+MD5_INIT, MD5_FINAL = 1, 2  # hf3fs_crc_md5_batch flags
+
+
+def md5_seg_dtype():
+    """numpy dtype of hf3fs_crc_md5_seg (include/hf3fs_crc.h): one 16-byte record per segment."""
+    import numpy as np
+    return np.dtype([("data", "<u8"), ("length", "<u8")])
+
+
+def md5_state_dtype():
+    """numpy dtype of hf3fs_crc_md5_state (include/hf3fs_crc.h): one 96-byte record per file."""
+    import numpy as np
+    return np.dtype([("h", "<u4", (4,)), ("total", "<u8"), ("tail", "u1", (64,)), ("reserved", "<u8")])
+
+
+def md5_batch(segs, file_off, n_files, n_segs, out=None, state=None, flags=MD5_INIT | MD5_FINAL, stream=None):
+    """hf3fs_crc_md5_batch: segs a device array of hf3fs_crc_md5_seg (md5_seg_dtype()), file_off
+    n_files + 1 device uint64, out 16 n_files device bytes (FINAL), state a device array of
+    hf3fs_crc_md5_state (md5_state_dtype()) or None (the one-shot form, INIT | FINAL)."""
+    return check(load().hf3fs_crc_md5_batch(_p(segs), _p(file_off), n_files, n_segs, _p(state), _p(out), flags,
+                                            _s(stream)))
+
+
+def md5_scratch_bytes(n_files):
+    """Bytes of library-owned scratch one md5_batch of n_files takes (0: a rejected count)."""
+    return int(load().hf3fs_crc_md5_scratch_bytes(n_files))
+
+
+def md5_hex(digest):
+    """16 digest bytes -> the 32 lower-case hex characters the admin command prints."""
+    b = bytes(digest)
+    if len(b) != 16:
+        raise ValueError("an MD5 digest has 16 bytes")
+    src = ctypes.create_string_buffer(b, 16)
+    out = ctypes.create_string_buffer(32)
+    k = load().hf3fs_crc_md5_hex(src, out)
+    return out.raw[:k].decode()
 
 
 def scrub_batch(ctype, ios, n, max_len, count, stream=None):

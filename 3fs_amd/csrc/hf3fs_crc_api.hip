@@ -27,6 +27,7 @@
 #include "digest_kernels.h"
 #include "engine_kernels.h"
 #include "internal.h"
+#include "md5_kernels.h"
 #include "options.h"
 #include "order_kernels.h"
 #include "sync_kernels.h"
@@ -40,6 +41,7 @@ static_assert(sizeof(hf3fs_crc_block_digest) == 24, "hf3fs_crc_block_digest ABI 
 static_assert(sizeof(hf3fs_crc_file_digest) == 24, "hf3fs_crc_file_digest ABI layout");
 static_assert(sizeof(hf3fs_crc_scrub_io) == 32, "hf3fs_crc_scrub_io ABI layout");
 static_assert(sizeof(hf3fs_crc_sync_meta) == 48, "hf3fs_crc_sync_meta ABI layout");
+static_assert(sizeof(hf3fs_crc_md5_seg) == 16 && sizeof(hf3fs_crc_md5_state) == 96, "hf3fs_crc_md5 ABI layout");
 static_assert(sizeof(hf3fs_crc_frame) == 24, "hf3fs_crc_frame ABI layout");
 static_assert(sizeof(hf3fs_crc_engine_meta) == 120, "hf3fs_crc_engine_meta ABI layout");
 static_assert(sizeof(hf3fs_crc_anomaly) == 72, "hf3fs_crc_anomaly ABI layout");
@@ -245,6 +247,9 @@ int is_capturing(hipStream_t s, bool* capturing) {
   return HF3FS_CRC_OK;
 }
 
+// What a roomy pair buffer of `words` is sized to when it is first made.
+constexpr size_t roomy_words(size_t words) { return (words + 65535) / 65536 * 65536; }
+
 std::atomic<uint64_t> g_pair_allocs{0};  // allocations and growths of pair buffers (hf3fs_crc_pair_scratch_stats)
 
 // The calling (stream, thread) pair's buffer `member`, at least `words` long (roomy: sized
@@ -265,7 +270,7 @@ int pair_buffer(Context* c, Scratch PairState::*member, hipStream_t s, size_t wo
   }
   if (e.words < words) {
     g_pair_allocs.fetch_add(1, std::memory_order_relaxed);
-    const size_t grow_to = roomy ? std::max<size_t>((words + 65535) / 65536 * 65536, 2 * e.words) : words;
+    const size_t grow_to = roomy ? std::max<size_t>(roomy_words(words), 2 * e.words) : words;
     hipError_t err = e.ptr ? hipStreamSynchronize(s) : hipSuccess;
     if (err == hipSuccess && e.ptr) {
       err = hipFree(e.ptr);
@@ -1318,6 +1323,47 @@ int hf3fs_crc_sync_plan(hf3fs_crc_sync_meta* d_local, uint64_t n_local, hf3fs_cr
   sync_scratch_carve(base, n_local, n_remote, &ss);
   HIP_OR_FAIL(launch_sync_plan(d_local, n_local, d_remote, n_remote, chain_ver, flags, d_write, d_remove, d_info, ss, s));
   return HF3FS_CRC_OK;
+}
+
+size_t hf3fs_crc_md5_scratch_bytes(uint64_t n_files) {
+  if (n_files > kMd5MaxCount) return 0;
+  // What the pair's buffer is sized to by a first call of n_files (a captured call's own memory is
+  // the carve's exact bytes, which are fewer).
+  return roomy_words((md5_scratch_bytes(n_files) + 3) / 4) * 4;
+}
+
+int hf3fs_crc_md5_batch(const hf3fs_crc_md5_seg* d_segs, const uint64_t* d_file_off, uint64_t n_files, uint64_t n_segs,
+                        hf3fs_crc_md5_state* d_state, uint8_t* d_out, uint32_t flags, void* stream) {
+  if (n_files == 0) return HF3FS_CRC_OK;
+  if (!d_file_off) return fail(HF3FS_CRC_INVALID_ARG, "null file offsets");
+  if (n_segs && !d_segs) return fail(HF3FS_CRC_INVALID_ARG, "null segments");
+  constexpr uint32_t kBoth = HF3FS_MD5_INIT | HF3FS_MD5_FINAL;
+  if (flags & ~kBoth) return fail(HF3FS_CRC_INVALID_ARG, "unknown flags %#x", flags);
+  if (!d_state && flags != kBoth) return fail(HF3FS_CRC_INVALID_ARG, "null state needs INIT | FINAL");
+  if ((flags & HF3FS_MD5_FINAL) && !d_out) return fail(HF3FS_CRC_INVALID_ARG, "FINAL with null output");
+  if (n_files > kMd5MaxCount || n_segs > kMd5MaxCount)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many files or segments (%llu, %llu)", (unsigned long long)n_files,
+                (unsigned long long)n_segs);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, md5_scratch_bytes(n_files), &base)) return rc;
+  Md5Scratch ms;
+  md5_scratch_carve(base, n_files, &ms);
+  const Options& o = options();
+  HIP_OR_FAIL(launch_md5_batch(d_segs, d_file_off, n_files, n_segs, d_state, d_out, flags, o.md5_sort.load() != 0,
+                               o.md5_stage.load() != 0, ms, s));
+  return HF3FS_CRC_OK;
+}
+
+uint32_t hf3fs_crc_md5_hex(const uint8_t* digest16, char* out32) {
+  static const char kHex[] = "0123456789abcdef";
+  for (int i = 0; i < 16; ++i) {
+    out32[2 * i] = kHex[digest16[i] >> 4];
+    out32[2 * i + 1] = kHex[digest16[i] & 15];
+  }
+  return 32;
 }
 
 int hf3fs_crc_sync_scrub_fill(const hf3fs_crc_sync_meta* d_local, const uint64_t* d_addrs, const uint32_t* d_write,

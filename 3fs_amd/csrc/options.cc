@@ -52,6 +52,8 @@ const Spec* specs(size_t* n) {
       {"range_stream", &o.range_stream, nullptr, 0, 1, {}},
       {"list_runs", &o.list_runs, nullptr, 0, 1, {}},
       {"fault_io", nullptr, &o.fault_io, 0, 0xFFFFFFFFll, {}, true},
+      {"md5_sort", &o.md5_sort, nullptr, 0, 1, {}},
+      {"md5_stage", &o.md5_stage, nullptr, 0, 1, {}},
   };
   *n = sizeof(s) / sizeof(s[0]);
   return s;

@@ -34,6 +34,9 @@ struct Options {
   std::atomic<int> audit{1};               // audit: re-hash every payload reported as mismatched (§7)
   std::atomic<int> range_stream{0};        // range_stream: balanced whole-range tasks as one block stream per wave
   std::atomic<int> list_runs{0};           // list_runs: create_batch hashes its ranges as byte runs (A/B, probes)
+  std::atomic<int> md5_sort{0};            // md5_sort: md5_batch lanes take the files bucketed by block count
+  std::atomic<int> md5_stage{0};           // md5_stage: md5_batch waves stage the lanes' pieces through LDS
+                                           // (both A/B: profiles/md5_batch.jsonl)
   std::atomic<uint32_t> fault_io{0};       // fault_io (test only): IO fault_io - 1 of every update batch hashes
                                            // its payload from a wrong start value (exercises the audit)
 };

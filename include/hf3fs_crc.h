@@ -107,7 +107,9 @@ int hf3fs_crc_graph_scratch_stats(uint64_t *live_buffers, uint64_t *live_bytes, 
  * poison (every library scratch word handed to a call -- verify values, call scratch and
  * the byte-balance region -- is first set to this value, 0 = off) and fault_io (IO
  * fault_io - 1 of every update batch is hashed from a wrong start value, 0 = off: the
- * self-check's end-to-end test). */
+ * self-check's end-to-end test).
+ * Switches of hf3fs_crc_md5_batch alone, described with the call: md5_sort (0|1) and
+ * md5_stage (0|1). */
 int hf3fs_crc_set_option(const char *name, const char *value);
 int hf3fs_crc_get_option(const char *name, char *out, size_t cap);
 
@@ -684,6 +686,69 @@ enum { HF3FS_DIGEST_FILL_ZERO = 1 };
 int hf3fs_crc_file_digest_batch_ex(const hf3fs_crc_block_digest *d_blocks, const uint64_t *d_file_off,
                                    hf3fs_crc_file_digest *d_out, uint64_t n_files, uint64_t max_blocks,
                                    uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* file MD5: admin `checksum --md5`                                           */
+/* ------------------------------------------------------------------------ */
+/* One run of bytes of a file, in file order. data == 0: `length` zero bytes (a hole). */
+typedef struct hf3fs_crc_md5_seg {
+  uint64_t data;            /* device address of the bytes (any alignment), 0 = a hole */
+  uint64_t length;          /* bytes, 0 allowed */
+} hf3fs_crc_md5_seg;
+
+/* MD5_CTX between calls. tail[0, total % 64) = bytes not yet compressed; the call writes
+ * the rest of tail as zero (and reserved as 0), so a state is a deterministic function of the
+ * bytes seen. */
+typedef struct hf3fs_crc_md5_state {
+  uint32_t h[4];            /* A, B, C, D */
+  uint64_t total;           /* message bytes seen so far */
+  uint8_t tail[64];
+  uint64_t reserved;
+} hf3fs_crc_md5_state;
+
+enum { HF3FS_MD5_INIT = 1, HF3FS_MD5_FINAL = 2 };
+
+/* The MD5 leg of the admin command (src/client/cli/admin/Checksum.cc:50-83: MD5_Init, one
+ * MD5_Update per buffer fill in file order through FileWrapper.cc:172-177, MD5_Final) for n_files
+ * files at once, one GPU lane per file.  File f owns segments [d_file_off[f], d_file_off[f+1]) of
+ * d_segs, the indexing of hf3fs_crc_file_digest_batch; its message is the concatenation of its
+ * segments' bytes.  Segments may have any address alignment and any length, 0 included; a file
+ * may have no segments.  n_segs is the caller's statement of d_file_off[n_files] (the call reads
+ * nothing back); a wrong n_segs is undefined behaviour.
+ * HF3FS_MD5_INIT: every file starts from the RFC 1321 initial state; without it file f continues
+ * from d_state[f].  HF3FS_MD5_FINAL: the padding and the 64-bit bit length (total * 8 mod 2^64)
+ * are applied and d_out[16 f .. 16 f + 16) receives the digest in MD5_Final's byte order;
+ * d_state[f], when given, is left unchanged (the state before the padding).  Without FINAL
+ * d_state[f] receives the running state and d_out is ignored.  d_state == NULL needs INIT | FINAL
+ * (the one-shot form); a call with neither flag is a pure MD5_Update.  One call per buffer fill
+ * with d_state carried is the reference's loop.
+ * Holes -- a deliberate difference: data == 0 hashes zeros.  The reference's `--md5 --fillZero`
+ * hashes whatever its unzeroed RDMA buffer held for a hole (FileWrapper.cc:140-152 never touches
+ * the buffer), a quirk and no contract; this call gives the MD5 of the file with holes as zeros,
+ * which is what the CRC leg computes for the same option.
+ * Errors, all checked before any device is touched: n_files == 0 is OK; null d_file_off, n_segs >
+ * 0 with null d_segs, unknown flag bits, d_state == NULL unless both flags are set, FINAL with
+ * null d_out, n_files or n_segs above 2^30 -> kInvalidArg.
+ * Aliasing: d_out and d_state overlap no segment and not each other; anything else is undefined.
+ * Stream behaviour follows hf3fs_crc_sync_plan: asynchronous on `stream`, no host synchronisation,
+ * nothing read back; capturable, also as the process's first library call; a replayed graph
+ * re-plans from what d_segs, d_file_off and d_state hold at replay time.  Scratch per (stream,
+ * thread) pair outside a capture and graph-owned inside one, never the stream-ordered pool; every
+ * scratch word read is written by the call first (option poison).
+ * Options honoured: md5_sort (1: lanes take the files bucketed by length, so the 64 files of a
+ * wave end together; 0: in file order) and md5_stage (0: every lane loads its own 64 bytes; 1: the
+ * wave stages the lanes' next pieces through LDS with coalesced loads).  The result is the same
+ * under all four settings. */
+int hf3fs_crc_md5_batch(const hf3fs_crc_md5_seg *d_segs, const uint64_t *d_file_off, uint64_t n_files,
+                        uint64_t n_segs, hf3fs_crc_md5_state *d_state, uint8_t *d_out, uint32_t flags,
+                        void *stream);
+/* Bytes of scratch one such call takes, its full need: what a (stream, thread) pair's buffer
+ * is sized to by a first call of n_files (12 bytes per file and a table of up to 256 KiB, rounded up to the
+ * buffer's 256 KiB granule; a captured call's own memory is the unrounded figure).  Monotone in
+ * n_files: after one call of the largest n_files nothing grows.  0 for a count the call rejects. */
+size_t hf3fs_crc_md5_scratch_bytes(uint64_t n_files);
+/* host: fmt "{:02x}" join of 16 digest bytes (Checksum.cc:148) into out32, no terminator; returns 32 */
+uint32_t hf3fs_crc_md5_hex(const uint8_t *digest16, char *out32);
 
 /* ------------------------------------------------------------------------ */
 /* stored-chunk scrub against persisted checksums         */
