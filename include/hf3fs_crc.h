@@ -701,7 +701,7 @@ typedef struct hf3fs_crc_md5_seg {
  * bytes seen. */
 typedef struct hf3fs_crc_md5_state {
   uint32_t h[4];            /* A, B, C, D */
-  uint64_t total;           /* message bytes seen so far */
+  uint64_t total;           /* message bytes seen so far, mod 2^64 (see below) */
   uint8_t tail[64];
   uint64_t reserved;
 } hf3fs_crc_md5_state;
@@ -722,6 +722,9 @@ enum { HF3FS_MD5_INIT = 1, HF3FS_MD5_FINAL = 2 };
  * d_state[f] receives the running state and d_out is ignored.  d_state == NULL needs INIT | FINAL
  * (the one-shot form); a call with neither flag is a pure MD5_Update.  One call per buffer fill
  * with d_state carried is the reference's loop.
+ * total is a full 64-bit count and wraps at 2^64 bytes.  The wrap loses nothing the digest needs:
+ * total % 64 and total * 8 mod 2^64 are the same before and after it, and the bit count mod 2^64 is
+ * all MD5_Update keeps (Nl, Nh), so a stream that passes 2^64 bytes still gets MD5_Final's digest.
  * Holes -- a deliberate difference: data == 0 hashes zeros.  The reference's `--md5 --fillZero`
  * hashes whatever its unzeroed RDMA buffer held for a hole (FileWrapper.cc:140-152 never touches
  * the buffer), a quirk and no contract; this call gives the MD5 of the file with holes as zeros,

@@ -12,6 +12,13 @@
 // Usage:  fuzz_md5 <case file>       prints one JSON line with what the cases covered
 //
 // A line of the case file:  residue digest content-hex|- ncalls { nsegs { kind length } }
+// or, a file that is one hole:  H length digest
+// The second kind takes totals past 2^29 bytes (a bit length that needs its upper word) through the
+// core where bytes cost nothing: an INIT call over the hole leaves the state just before the
+// padding, which is printed as its own JSON line {"hole", "h", "total"} (tests/md5_queue.py keeps
+// these as seeds for the GPU), a FINAL call without segments from that state gives the digest, and
+// below 2^30 bytes the one-shot call must give it too.  Only the block path of the kernel is walked:
+// the byte cursor over 2^32 zeros is the same 64 bytes 2^26 times.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,7 +36,7 @@ static_assert(sizeof(hf3fs_crc_md5_seg) == 16 && sizeof(hf3fs_crc_md5_state) == 
 
 struct Counts {
   uint64_t cases = 0, calls = 0, granule_blocks = 0, hole_blocks = 0, cursor_blocks = 0, pad_one = 0, pad_two = 0,
-           holes = 0, empty_segs = 0, empty_calls = 0;
+           holes = 0, empty_segs = 0, empty_calls = 0, long_holes = 0;
   uint64_t tails = 0;     // bit t: a call began with t carried bytes
   uint32_t residues = 0;  // bit r: a granule block began r bytes into a granule
 };
@@ -99,6 +106,29 @@ static void run_call(const Call& c, uint32_t flags, hf3fs_crc_md5_state* state, 
   }
 }
 
+static void run_long_hole(size_t lineno, uint64_t length, const std::string& want, Counts* n) {
+  Call hole, none;
+  hole.segs.push_back({0, length});
+  hf3fs_crc_md5_state state;
+  memset(&state, 0xA5, sizeof(state));
+  uint8_t digest[16] = {};
+  run_call(hole, HF3FS_MD5_INIT, &state, digest, true, n);
+  if (state.total != length || state.reserved) fail(lineno, "state total of a hole");
+  for (unsigned i = 0; i < 64; ++i)
+    if (state.tail[i]) fail(lineno, "state tail of a hole");
+  printf("{\"hole\": %llu, \"h\": [%u, %u, %u, %u], \"total\": %llu}\n", (unsigned long long)length, state.h[0],
+         state.h[1], state.h[2], state.h[3], (unsigned long long)state.total);
+  const hf3fs_crc_md5_state before = state;
+  run_call(none, HF3FS_MD5_FINAL, &state, digest, true, n);
+  if (memcmp(&before, &state, sizeof(before))) fail(lineno, "FINAL changed the state");
+  if (hex(digest, 16) != want) fail(lineno, ("digest of a hole " + hex(digest, 16) + " != " + want).c_str());
+  if (length < (1ull << 30)) {
+    run_call(hole, HF3FS_MD5_INIT | HF3FS_MD5_FINAL, nullptr, digest, true, n);
+    if (hex(digest, 16) != want) fail(lineno, "one-shot digest of a hole");
+  }
+  ++n->long_holes;
+}
+
 int main(int argc, char** argv) {
   if (argc != 2) {
     fprintf(stderr, "usage: fuzz_md5 <case file>\n");
@@ -116,6 +146,16 @@ int main(int argc, char** argv) {
   while (std::getline(in, line)) {
     ++lineno;
     if (line.empty()) continue;
+    if (line[0] == 'H') {
+      std::istringstream hs(line.substr(1));
+      uint64_t length = 0;
+      std::string want;
+      hs >> length >> want;
+      if (!hs || want.size() != 32) fail(lineno, "bad hole line");
+      run_long_hole(lineno, length, want, &n);
+      ++n.cases;
+      continue;
+    }
     std::istringstream ls(line);
     unsigned residue = 0, ncalls = 0;
     std::string want, content_hex;
@@ -200,10 +240,10 @@ int main(int argc, char** argv) {
   }
   printf("{\"fuzz_md5\": \"ok\", \"cases\": %llu, \"calls\": %llu, \"granule_blocks\": %llu, \"hole_blocks\": %llu, "
          "\"cursor_blocks\": %llu, \"pad_one\": %llu, \"pad_two\": %llu, \"holes\": %llu, \"empty_segs\": %llu, "
-         "\"empty_calls\": %llu, \"tail_lengths\": %d, \"residues\": %d}\n",
+         "\"empty_calls\": %llu, \"long_holes\": %llu, \"tail_lengths\": %d, \"residues\": %d}\n",
          (unsigned long long)n.cases, (unsigned long long)n.calls, (unsigned long long)n.granule_blocks,
          (unsigned long long)n.hole_blocks, (unsigned long long)n.cursor_blocks, (unsigned long long)n.pad_one,
          (unsigned long long)n.pad_two, (unsigned long long)n.holes, (unsigned long long)n.empty_segs,
-         (unsigned long long)n.empty_calls, __builtin_popcountll(n.tails), __builtin_popcount(n.residues));
+         (unsigned long long)n.empty_calls, (unsigned long long)n.long_holes, __builtin_popcountll(n.tails), __builtin_popcount(n.residues));
   return 0;
 }
