@@ -15,8 +15,14 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libhf3fs_crc.so")
 SOURCES = ["crc_kernels.hip", "update_kernels.hip", "order_kernels.hip", "version_kernels.hip", "engine_kernels.hip", "sync_kernels.hip", "digest_kernels.hip", "md5_kernels.hip", "hf3fs_crc_api.hip",
            "capture_scratch.hip", "device_tables.cc", "coalescer.hip", "aux_kernels.hip", "frame_kernels.hip", "host_codec.cc", "options.cc"]
-HEADERS = ["crc_kernels.h", "crc_device.h", "update_kernels.h", "update_plan.h", "order_kernels.h", "version_kernels.h", "version_plan.h", "engine_kernels.h", "engine_plan.h", "sync_kernels.h", "sync_plan.h", "digest_kernels.h", "md5_kernels.h", "md5_core.h", "gf2.h", "internal.h", "capture_scratch.h", "aux_kernels.h", "frame_kernels.h", "options.h"]
+HEADERS = ["loadcheck.h", "crc_kernels.h", "crc_device.h", "update_kernels.h", "update_plan.h", "order_kernels.h", "version_kernels.h", "version_plan.h", "engine_kernels.h", "engine_plan.h", "sync_kernels.h", "sync_plan.h", "digest_kernels.h", "md5_kernels.h", "md5_core.h", "gf2.h", "internal.h", "capture_scratch.h", "aux_kernels.h", "frame_kernels.h", "options.h"]
 ARCH = os.environ.get("HF3FS_CRC_ARCH", "gfx950")
+# The load-checked library (csrc/loadcheck.h, tests/test_gpu_load_footprint.py): the units whose
+# kernels load caller bytes are compiled again with the switch, the others' objects are shared.
+CHECK_LIB = os.path.join(LIBDIR, "libhf3fs_crc_loadcheck.so")
+CHECK_SOURCES = ["crc_kernels.hip", "update_kernels.hip", "frame_kernels.hip", "md5_kernels.hip", "aux_kernels.hip",
+                 "order_kernels.hip", "version_kernels.hip", "engine_kernels.hip"]
+CHECK_ONLY = ["loadcheck.hip"]
 
 
 def _stale(target, deps):
@@ -48,15 +54,27 @@ def build(force=False, verbose=False):
         objs.append(obj)
         if force or _stale(obj, [src] + common):
             jobs.append((["hipcc", f"--offload-arch={ARCH}"] + flags + ["-c", src, "-o", obj], verbose))
+    # the check library's own objects, in a directory of their own
+    cdir = os.path.join(REPO, "build", "obj_loadcheck")
+    os.makedirs(cdir, exist_ok=True)
+    cobjs = []
+    for name in CHECK_SOURCES + CHECK_ONLY:
+        src = os.path.join(CSRC, name)
+        obj = os.path.join(cdir, name + ".o")
+        cobjs.append(obj)
+        if force or _stale(obj, [src] + common):
+            jobs.append((["hipcc", f"--offload-arch={ARCH}"] + flags + ["-DHF3FS_CRC_LOAD_CHECK", "-c", src, "-o", obj],
+                         verbose))
+    cobjs += [o for o, s in zip(objs, SOURCES) if s not in CHECK_SOURCES]
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as ex:
             list(ex.map(_compile, jobs))
-    if not force and not jobs and not _stale(LIB, objs):
-        return LIB
-    cmd = ["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+    for lib, its in ((LIB, objs), (CHECK_LIB, cobjs)):
+        if force or jobs or _stale(lib, its):
+            cmd = ["hipcc", f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib] + its
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            subprocess.check_call(cmd)
     return LIB
 
 

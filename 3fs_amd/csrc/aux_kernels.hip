@@ -1,6 +1,7 @@
 // aux_kernels.hip -- see aux_kernels.h.  The bytes are hashed by k_crc_ranges
 // between prep and finalize; these kernels only move 24-32 B records.
 #include "aux_kernels.h"
+#include "loadcheck.h"
 #include "gf2.h"
 
 namespace hf3fs_crc {
@@ -21,7 +22,7 @@ __device__ __forceinline__ void count_bad(uint32_t bad, uint32_t* count) {
 __global__ void k_scrub_prep(hf3fs_crc_scrub_io* __restrict__ ios, uint64_t n, uint8_t type, uint32_t max_len,
                              uint64_t* __restrict__ addr, uint64_t* __restrict__ len, uint32_t* __restrict__ maxl) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    hf3fs_crc_scrub_io io = ios[i];
+    hf3fs_crc_scrub_io io = HF3FS_LC_REC(ios, i, n);
     const bool typed = io.checksum_type != kTypeNone;
     const bool ok = (!typed || io.checksum_type == type) && io.length <= max_len && (io.data || !io.length) &&
                     io.fin <= 1;
@@ -42,7 +43,7 @@ __global__ void k_scrub_finalize(hf3fs_crc_scrub_io* __restrict__ ios, uint64_t 
                                  uint32_t* __restrict__ count) {
   uint32_t bad = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    hf3fs_crc_scrub_io io = ios[i];
+    hf3fs_crc_scrub_io io = HF3FS_LC_REC(ios, i, n);
     if (io.status != HF3FS_CRC_OK) {
       ++bad;
       continue;

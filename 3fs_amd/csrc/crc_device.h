@@ -10,6 +10,7 @@
 //     old bytes a write overwrites.
 #pragma once
 #include "crc_kernels.h"
+#include "loadcheck.h"
 
 namespace hf3fs_crc {
 
@@ -24,18 +25,20 @@ typedef __attribute__((address_space(1))) u32x4 g_u32x4;
 
 // global_load_dwordx4 (address space 1, not flat: flat loads would also count
 // on lgkmcnt and serialise against the LDS table reads).
-__device__ __forceinline__ uint4 gload16(uint64_t addr) {
+__device__ __forceinline__ uint4 gload16(uint64_t addr, uint32_t site = kSiteGload16) {
+  if (!lc_ok(addr, 16, site)) return make_uint4(0, 0, 0, 0);
   const u32x4 v = *reinterpret_cast<g_cu32x4*>(addr);
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 // The streamed body of a range: optionally non-temporal (read-once data).
 template <bool NT>
-__device__ __forceinline__ uint4 gload16s(uint64_t addr) {
+__device__ __forceinline__ uint4 gload16s(uint64_t addr, uint32_t site = kSiteGload16s) {
   if (NT) {
+    if (!lc_ok(addr, 16, site)) return make_uint4(0, 0, 0, 0);
     const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<g_cu32x4*>(addr));
     return make_uint4(v.x, v.y, v.z, v.w);
   }
-  return gload16(addr);
+  return gload16(addr, site);
 }
 
 // Bytes [lo, hi) of dword `d` (byte positions 4d..4d+3 of a granule) kept.
@@ -55,7 +58,7 @@ __device__ __forceinline__ uint4 gload16_masked(uint64_t g, uint64_t lo, uint64_
   uint64_t a = lo > g ? lo : g;
   uint64_t b = hi < g + 16 ? hi : g + 16;
   if (a >= b) return make_uint4(0, 0, 0, 0);
-  uint4 w = gload16(g);
+  uint4 w = gload16(g, kSiteGloadMasked);
   int s = (int)(a - g), e = (int)(b - g);
   w.x &= dword_mask(s, e, 0);
   w.y &= dword_mask(s, e, 1);
@@ -375,8 +378,14 @@ __device__ __forceinline__ uint32_t xpow_pair(int64_t eA, int64_t eB, int lane, 
 }
 
 
+// One caller byte (the partial granules at the ends of a copy).
+__device__ __forceinline__ uint8_t load_byte(uint64_t a, uint32_t site) {
+  if (!lc_ok(a, 1, site)) return 0;
+  return *reinterpret_cast<const uint8_t*>(a);
+}
 template <bool NT = false>
-__device__ __forceinline__ u32x4 ld16(uint64_t a) {
+__device__ __forceinline__ u32x4 ld16(uint64_t a, uint32_t site = kSiteLd16) {
+  if (!lc_ok(a, 16, site)) return u32x4{0, 0, 0, 0};
   if (NT) return __builtin_nontemporal_load(reinterpret_cast<g_cu32x4*>(a));
   return *reinterpret_cast<g_cu32x4*>(a);
 }
@@ -393,9 +402,9 @@ template <bool NT = false>
 __device__ __forceinline__ u32x4 ld16_unaligned(uint64_t S) {
   const uint64_t Sg = S & ~uint64_t(15);
   const uint32_t sh = (uint32_t)(S & 15);
-  const u32x4 A = ld16<NT>(Sg);
+  const u32x4 A = ld16<NT>(Sg, kSiteLd16Unaligned);
   if (sh == 0) return A;
-  const u32x4 B = ld16<NT>(Sg + 16);
+  const u32x4 B = ld16<NT>(Sg + 16, kSiteLd16Unaligned);
   uint32_t w[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
   const uint32_t q = sh >> 2, r = sh & 3;
   uint32_t t[5];
@@ -492,7 +501,7 @@ __device__ __forceinline__ uint32_t wg_write_hash_old(uint64_t dst, uint64_t src
         } else if (g < d1 && g + 16 > dst) {  // the partial first / last granule of the write
           const uint64_t lo = g > dst ? g : dst, hi = g + 16 < d1 ? g + 16 : d1;
           for (uint64_t q = lo; q < hi; ++q)
-            *reinterpret_cast<uint8_t*>(q) = *reinterpret_cast<const uint8_t*>(src + (q - dst));
+            *reinterpret_cast<uint8_t*>(q) = load_byte(src + (q - dst), kSiteCopyByte);
         }
       }
     }

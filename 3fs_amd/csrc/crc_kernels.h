@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "gf2.h"
+#include "loadcheck.h"
 
 namespace hf3fs_crc {
 
@@ -120,9 +121,9 @@ struct ListSource {
   const uint32_t* starts;  // nullable: ~0U
   uint64_t n;
   uint32_t default_start;
-  __device__ uint64_t addr(uint64_t i) const { return addrs[i]; }
-  __device__ uint64_t length(uint64_t i) const { return lens[i]; }
-  __device__ uint32_t start_of(uint64_t i) const { return starts ? starts[i] : default_start; }
+  __device__ uint64_t addr(uint64_t i) const { return lc_desc_ok(i, n) ? addrs[i] : 0; }
+  __device__ uint64_t length(uint64_t i) const { return lc_desc_ok(i, n) ? lens[i] : 0; }
+  __device__ uint32_t start_of(uint64_t i) const { return starts ? (lc_desc_ok(i, n) ? starts[i] : 0u) : default_start; }
 };
 
 struct ArenaSource {  // KVCache blocks addressed by offset into one arena
@@ -130,8 +131,8 @@ struct ArenaSource {  // KVCache blocks addressed by offset into one arena
   const uint64_t* offsets;
   const uint32_t* lens;
   uint64_t n;
-  __device__ uint64_t addr(uint64_t i) const { return base + offsets[i]; }
-  __device__ uint64_t length(uint64_t i) const { return lens[i]; }
+  __device__ uint64_t addr(uint64_t i) const { return lc_desc_ok(i, n) ? base + offsets[i] : 0; }
+  __device__ uint64_t length(uint64_t i) const { return lc_desc_ok(i, n) ? lens[i] : 0; }
   __device__ uint32_t start_of(uint64_t) const { return ~0u; }
 };
 

@@ -63,7 +63,7 @@ __device__ __forceinline__ void direct_pipe(const Src& src, uint32_t t, uint32_t
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const uint64_t g = cur.vs + k * kBlockBytes + lane_off;
-      pre[k] = k < cur.nb && g < cur.a0 + cur.len && g + 16 > cur.a0 ? gload16s<NT>(g) : make_uint4(0, 0, 0, 0);
+      pre[k] = k < cur.nb && g < cur.a0 + cur.len && g + 16 > cur.a0 ? gload16s<NT>(g, kSiteDirectPre) : make_uint4(0, 0, 0, 0);
     }
   }
   while (t < ntasks) {
@@ -112,7 +112,7 @@ __device__ __forceinline__ void direct_pipe(const Src& src, uint32_t t, uint32_t
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const uint64_t g = cur.vs + k * kBlockBytes + lane_off;
-        pre[k] = k < cur.nb && g < cur.a0 + cur.len && g + 16 > cur.a0 ? gload16s<NT>(g) : make_uint4(0, 0, 0, 0);
+        pre[k] = k < cur.nb && g < cur.a0 + cur.len && g + 16 > cur.a0 ? gload16s<NT>(g, kSiteDirectPre) : make_uint4(0, 0, 0, 0);
       }
     }
     uint32_t r = start;  // create(type, buf, 0, start) == {type, start}
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void k_crc_range_stream(Src src, uint32_t
     const uint64_t glo = pg.a0 & ~uint64_t(15), ghi = (pg.a1 - 1) & ~uint64_t(15);
     uint64_t g = pg.vs + (uint64_t)pk * kBlockBytes + lane_off;
     g = g < glo ? glo : (g > ghi ? ghi : g);  // edge blocks: granules outside the range re-read a valid one
-    const uint4 v = gload16s<NT>(g);
+    const uint4 v = gload16s<NT>(g, kSiteStreamProduce);
     if (pdone) return v;
     if (++pk == pg.nb) {  // next non-empty task
       pk = 0;

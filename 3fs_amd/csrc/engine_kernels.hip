@@ -1,6 +1,7 @@
 // engine_kernels.hip -- see engine_kernels.h.  Like the order and version kernels these only move
 // records and indices; the bytes are hashed and written by the update pipeline between the steps.
 #include "engine_kernels.h"
+#include "loadcheck.h"
 
 #include "engine_plan.h"
 #include "update_plan.h"
@@ -127,8 +128,8 @@ __global__ __launch_bounds__(256) void k_engine_step(const StepArgs a) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t ri = a.rank[i];
     if (a.r > 0 && ri == a.r - 1) {
-      const hf3fs_crc_update_io me = a.ios[i];
-      const hf3fs_crc_engine_job job = a.jobs[i];
+      const hf3fs_crc_update_io me = HF3FS_LC_REC(a.ios, i, a.n);
+      const hf3fs_crc_engine_job job = HF3FS_LC_REC(a.jobs, i, a.n);
       EngState after;
       if (a.dec[i] == 0u) {
         const hf3fs_crc_update_io o = a.round[i];
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(256) void k_engine_step(const StepArgs a) {
       }
       const uint32_t j = a.succ[i];
       if (!last && j != kOrderNone && j < n) {
-        hf3fs_crc_update_io nx = a.ios[j];
-        hf3fs_crc_engine_job nj = a.jobs[j];
+        hf3fs_crc_update_io nx = HF3FS_LC_REC(a.ios, j, a.n);
+        hf3fs_crc_engine_job nj = HF3FS_LC_REC(a.jobs, j, a.n);
         store_before(&nx, &nj, after);
         store_before(&a.ios[j], &a.jobs[j], after);
         decide(a, j, nx, nj);
@@ -174,38 +175,38 @@ __global__ __launch_bounds__(256) void k_engine_step(const StepArgs a) {
           a.vlen[i] = 0;
         }
       } else if (a.r == 0) {
-        decide(a, (uint32_t)i, a.ios[i], a.jobs[i]);
+        decide(a, (uint32_t)i, HF3FS_LC_REC(a.ios, i, a.n), HF3FS_LC_REC(a.jobs, i, a.n));
       }
     } else if (ri >= a.max_rounds) {
       uint32_t p = a.pred[i];
       for (uint64_t steps = 0; steps < n && p < n && a.rank[p] >= a.max_rounds; ++steps) p = a.pred[p];
-      EngState st = load_before(a.ios[i], a.jobs[i]);
+      EngState st = load_before(HF3FS_LC_REC(a.ios, i, a.n), HF3FS_LC_REC(a.jobs, i, a.n));
       if (p < n) {
         // input fields and before-fields of p only: its thread is writing the outputs
         hf3fs_crc_update_io pio{};
-        pio.chunk_size = a.ios[p].chunk_size;
-        pio.chunk_checksum_type = a.ios[p].chunk_checksum_type;
-        pio.chunk_checksum = a.ios[p].chunk_checksum;
+        pio.chunk_size = HF3FS_LC_REC(a.ios, p, a.n).chunk_size;
+        pio.chunk_checksum_type = HF3FS_LC_REC(a.ios, p, a.n).chunk_checksum_type;
+        pio.chunk_checksum = HF3FS_LC_REC(a.ios, p, a.n).chunk_checksum;
         hf3fs_crc_engine_job pj{};
-        pj.addr = a.jobs[p].addr;
-        pj.chain_ver = a.jobs[p].chain_ver;
-        pj.chunk_ver = a.jobs[p].chunk_ver;
-        pj.w_addr = a.jobs[p].w_addr;
-        pj.w_len = a.jobs[p].w_len;
-        pj.w_checksum = a.jobs[p].w_checksum;
-        pj.w_chain_ver = a.jobs[p].w_chain_ver;
-        pj.w_chunk_ver = a.jobs[p].w_chunk_ver;
+        pj.addr = HF3FS_LC_REC(a.jobs, p, a.n).addr;
+        pj.chain_ver = HF3FS_LC_REC(a.jobs, p, a.n).chain_ver;
+        pj.chunk_ver = HF3FS_LC_REC(a.jobs, p, a.n).chunk_ver;
+        pj.w_addr = HF3FS_LC_REC(a.jobs, p, a.n).w_addr;
+        pj.w_len = HF3FS_LC_REC(a.jobs, p, a.n).w_len;
+        pj.w_checksum = HF3FS_LC_REC(a.jobs, p, a.n).w_checksum;
+        pj.w_chain_ver = HF3FS_LC_REC(a.jobs, p, a.n).w_chain_ver;
+        pj.w_chunk_ver = HF3FS_LC_REC(a.jobs, p, a.n).w_chunk_ver;
         if (a.dec[p] == 0u) {
           st = load_before(pio, pj);
           const hf3fs_crc_update_io o = a.round[p];
           if (o.status == HF3FS_CRC_OK) {
             const EngVerdict d =
-                engine_update(st, a.jobs[p].io_ver, a.jobs[p].job_chain_ver, a.jobs[p].dst, a.ios[p].update_type,
-                              a.ios[p].flags, a.ios[p].offset, a.ios[p].length, true);
+                engine_update(st, HF3FS_LC_REC(a.jobs, p, a.n).io_ver, HF3FS_LC_REC(a.jobs, p, a.n).job_chain_ver, HF3FS_LC_REC(a.jobs, p, a.n).dst, HF3FS_LC_REC(a.ios, p, a.n).update_type,
+                              HF3FS_LC_REC(a.ios, p, a.n).flags, HF3FS_LC_REC(a.ios, p, a.n).offset, HF3FS_LC_REC(a.ios, p, a.n).length, true);
             st = eng_written(d.next, o.out_size, o.out_checksum);
           }
         } else {
-          st = load_out(a.ios[p], a.jobs[p]);
+          st = load_out(HF3FS_LC_REC(a.ios, p, a.n), HF3FS_LC_REC(a.jobs, p, a.n));
         }
         store_before(&a.ios[i], &a.jobs[i], st);
       }
@@ -235,21 +236,21 @@ __global__ __launch_bounds__(256) void k_engine_settle(hf3fs_crc_update_io* __re
     uint32_t kind = 0;  // bit per info word 2..7
     if (i < n && rank[i] < max_rounds) {
       const uint32_t d = dec[i];
-      int32_t status = ios[i].status;
-      uint8_t detail = jobs[i].detail;
+      int32_t status = HF3FS_LC_REC(ios, i, n).status;
+      uint8_t detail = HF3FS_LC_REC(jobs, i, n).detail;
       if (((d >> kDecWhereShift) & 0xffu) == kEngLate) {
         status = (int32_t)(d & kDecStatusMask);
-        if ((d & kDecVerifyBit) && vout[i] != ios[i].write_checksum) {
+        if ((d & kDecVerifyBit) && vout[i] != HF3FS_LC_REC(ios, i, n).write_checksum) {
           status = HF3FS_CRC_CHECKSUM_MISMATCH;
           detail = HF3FS_ENGINE_DETAIL_NONE;
           jobs[i].detail = detail;
         }
         ios[i].status = status;
       }
-      const bool commit = ios[i].update_type == HF3FS_UPDATE_COMMIT;
+      const bool commit = HF3FS_LC_REC(ios, i, n).update_type == HF3FS_UPDATE_COMMIT;
       if (status == HF3FS_CRC_OK) {
         kind = commit ? 2u : 1u;
-        if (!commit) kind |= jobs[i].out_cow ? 8u : 16u;
+        if (!commit) kind |= HF3FS_LC_REC(jobs, i, n).out_cow ? 8u : 16u;
       } else {
         kind = 4u;
         if (status == HF3FS_CRC_INVALID_ARG && detail == HF3FS_ENGINE_DETAIL_IN_WRITING) kind |= 32u;

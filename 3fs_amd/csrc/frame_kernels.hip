@@ -20,11 +20,11 @@ __global__ __launch_bounds__(256) void k_frame_check(const hf3fs_crc_frame* __re
   uint32_t bad = 0;
   uint64_t pay = 0, gap = 0;  // payload bytes, bytes between payloads beyond the 8-byte headers
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t off = fr[i].offset, end = off + fr[i].size;
-    bad |= fr[i].size > max_size || end < off;
-    pay += fr[i].size;
+    const uint64_t off = HF3FS_LC_REC(fr, i, n).offset, end = off + HF3FS_LC_REC(fr, i, n).size;
+    bad |= HF3FS_LC_REC(fr, i, n).size > max_size || end < off;
+    pay += HF3FS_LC_REC(fr, i, n).size;
     if (i + 1 < n) {
-      const uint64_t next = fr[i + 1].offset;
+      const uint64_t next = HF3FS_LC_REC(fr, i + 1, n).offset;
       bad |= end > next;
       gap += next > end + kFrameHeaderBytes ? next - end - kFrameHeaderBytes : 0;
     }
@@ -67,7 +67,7 @@ __device__ void record_prep(const uint8_t* base, hf3fs_crc_frame* __restrict__ f
                             uint32_t* __restrict__ v, uint32_t* __restrict__ flags) {
   uint32_t mx = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    hf3fs_crc_frame f = frames[i];
+    hf3fs_crc_frame f = HF3FS_LC_REC(frames, i, n);
     const bool ok = f.size <= max_size;
     addr[i] = ok ? (uint64_t)(base + f.offset) : 0;
     len[i] = ok ? f.size : 0;
@@ -109,7 +109,7 @@ __global__ void k_frame_map(const uint8_t* base, hf3fs_crc_frame* __restrict__ f
                             int try_stream) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *count = 0;  // the finalize adds the mismatches
   const uint64_t b = (uint64_t)base;
-  const uint64_t lo = b + fr[0].offset, hi = b + fr[n - 1].offset + fr[n - 1].size;
+  const uint64_t lo = b + HF3FS_LC_REC(fr, 0, n).offset, hi = b + HF3FS_LC_REC(fr, n - 1, n).offset + HF3FS_LC_REC(fr, n - 1, n).size;
   const uint64_t a0 = lo & ~uint64_t(kBlockBytes - 1), hib = (hi & ~uint64_t(kBlockBytes - 1)) + kBlockBytes;
   const uint64_t blocks = (hib - a0) / kBlockBytes;
   const uint64_t sb = (blocks + seg_target - 1) / seg_target;  // blocks per segment
@@ -132,9 +132,9 @@ __global__ void k_frame_map(const uint8_t* base, hf3fs_crc_frame* __restrict__ f
   }
   uint32_t lng = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t s0 = b + fr[i].offset;
-    const uint64_t k1 = seg_of(s0 + fr[i].size, a0, (uint32_t)sb);
-    const uint64_t k0 = i ? seg_of(b + fr[i - 1].offset + fr[i - 1].size, a0, (uint32_t)sb) + 1 : 0;
+    const uint64_t s0 = b + HF3FS_LC_REC(fr, i, n).offset;
+    const uint64_t k1 = seg_of(s0 + HF3FS_LC_REC(fr, i, n).size, a0, (uint32_t)sb);
+    const uint64_t k0 = i ? seg_of(b + HF3FS_LC_REC(fr, i - 1, n).offset + HF3FS_LC_REC(fr, i - 1, n).size, a0, (uint32_t)sb) + 1 : 0;
     for (uint64_t k = k0; k <= k1; ++k) seg_first[k] = (uint32_t)i;
     lng |= k1 - seg_of(s0, a0, (uint32_t)sb) > kFrameHornerSegs;
   }
@@ -237,14 +237,14 @@ __global__ __launch_bounds__(kThreads) void k_frame_stream(const uint8_t* base, 
   auto load = [&](uint64_t blk) -> uint4 {
     uint64_t g = blk + lane_off;
     g = g < glo ? glo : (g > ghi ? ghi : g);
-    return gload16s<true>(g);
+    return gload16s<true>(g, kSiteFrameStream);
   };
   // frame f's (offset, size) for the window; f >= n reads frame n - 1 and is
   // turned into the never-reached position ~0 when the window is installed
   auto fetch = [&](uint64_t f, uint64_t& off, uint32_t& size) {
-    const hf3fs_crc_frame* p = fr + (f < n ? f : n - 1);
-    off = p->offset;
-    size = p->size;
+    const uint64_t k = f < n ? f : n - 1;
+    off = HF3FS_LC_REC(fr, k, n).offset;
+    size = HF3FS_LC_REC(fr, k, n).size;
   };
   // wave w takes segments [k0, k1): one contiguous byte range, so the block
   // prefetch and the frame window run on across segment boundaries
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(kThreads) void k_frame_stream(const uint8_t* base, 
   fetch(fw + lane, c_off, c_sz);
   fetch(fw + 64 + lane, n_off, n_sz);
   uint64_t prev_e = 0;  // payload end of frame fw - 1
-  if (fw > 0) prev_e = fb + fr[fw - 1].offset + fr[fw - 1].size;
+  if (fw > 0) prev_e = fb + HF3FS_LC_REC(fr, fw - 1, n).offset + HF3FS_LC_REC(fr, fw - 1, n).size;
   uint4 c[U];
 #pragma unroll
   for (int q = 0; q < U; ++q) {
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(kThreads) void k_frame_stream(const uint8_t* base, 
 #pragma unroll
           for (int q = 0; q < U; ++q) {
             const uint4 w = c[q];
-            c[q] = gload16s<true>(Ge + q * kBlockBytes + lane_off);
+            c[q] = gload16s<true>(Ge + q * kBlockBytes + lane_off, kSiteFrameStream);
             st.step(w, lj);
           }
         } else {
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(kThreads) void k_frame_stream(const uint8_t* base, 
       const uint4 w0 = c[q];
       const uint32_t nb_r = B_r + U * kBlockBytes;
       if (nb_r + kBlockBytes <= hfull_r && nb_r <= blast_r) {  // interior refill: no per-lane clamp
-        c[q] = gload16s<true>(b0 + nb_r + lane_off);
+        c[q] = gload16s<true>(b0 + nb_r + lane_off, kSiteFrameStream);
       } else {
         asm volatile("" ::: "memory");  // keeps this a branch (no if-conversion into both address forms)
         c[q] = load(b0 + (nb_r < blast_r ? nb_r : blast_r));
@@ -471,8 +471,8 @@ constexpr int kShLds = kShPow + 2 * 256;
 __device__ __forceinline__ uint32_t lin_t(uint64_t a, uint64_t b, const uint32_t* sh) {
   if (a >= b) return 0u;
   const uint64_t g = a & ~uint64_t(15);
-  const uint4 w0 = gload16(g);
-  const uint4 w1 = b > g + 16 ? gload16(g + 16) : make_uint4(0, 0, 0, 0);
+  const uint4 w0 = gload16(g, kSiteFramePair);
+  const uint4 w1 = b > g + 16 ? gload16(g + 16, kSiteFramePair) : make_uint4(0, 0, 0, 0);
   const uint32_t w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
   const int ja = (int)(a - g), jb = (int)(b - g);
   uint32_t c = 0;
@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256) void k_frame_finalize(const uint8_t* base, hf3
   }
   uint32_t bad = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    hf3fs_crc_frame f = frames[i];
+    hf3fs_crc_frame f = HF3FS_LC_REC(frames, i, n);
     uint32_t val;
     if (stream) {
       const uint64_t a0 = prm->a0, seg = prm->seg, lo = prm->lo;
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(256) void k_frame_finalize(const uint8_t* base, hf3
       const uint32_t sbk = (uint32_t)(seg >> 10);
       const uint64_t ks = seg_of(s, a0, sbk), ke = seg_of(e, a0, sbk);
       uint32_t qs;  // lin(segment ks before s), referenced at s
-      const uint64_t ep = i ? (uint64_t)base + frames[i - 1].offset + frames[i - 1].size : 0;
+      const uint64_t ep = i ? (uint64_t)base + HF3FS_LC_REC(frames, i - 1, n).offset + HF3FS_LC_REC(frames, i - 1, n).size : 0;
       if (i && s - ep <= kFrameGapMax) {  // start derived from the end before it
         qs = seg_of(ep, a0, sbk) == ks ? seg_lin_at<POLY>(ev[2 * i - 1], ep, s, lo, T, sh)
                                    : lin_t(a0 + ks * seg, s, sh);  // a segment starts in between

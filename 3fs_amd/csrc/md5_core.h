@@ -22,6 +22,13 @@
 #define HF3FS_MD5_ROLLED
 #endif
 
+// The load-checked build (loadcheck.h) routes the cursor's segment bytes through its check.
+#if defined(HF3FS_CRC_LOAD_CHECK) && defined(__HIP_DEVICE_COMPILE__)
+#define HF3FS_MD5_BYTE_OK(a) lc_ok((a), 1, kSiteMd5Byte)
+#else
+#define HF3FS_MD5_BYTE_OK(a) true
+#endif
+
 namespace hf3fs_crc {
 
 HF3FS_MD5_FN void md5_init(uint32_t h[4]) {
@@ -195,7 +202,10 @@ HF3FS_MD5_FN uint32_t md5_stream_byte(Md5Stream& s, bool pad) {
   }
   if (s.seg < s.seg_end) {
     uint32_t b = 0;
-    if (s.addr) b = *(const uint8_t*)(uintptr_t)s.addr++;
+    if (s.addr) {
+      if (HF3FS_MD5_BYTE_OK(s.addr)) b = *(const uint8_t*)(uintptr_t)s.addr;
+      ++s.addr;
+    }
     ++s.total;
     if (--s.rem == 0) {
       ++s.seg;

@@ -11,6 +11,7 @@
 // Nothing is read that an earlier launch of the same call has not written (option poison).
 #include "md5_kernels.h"
 
+#include "loadcheck.h"
 #include "md5_core.h"
 
 namespace hf3fs_crc {
@@ -159,11 +160,11 @@ __device__ __forceinline__ void load_granules(const uint64_t addr, uint32_t g[20
   const uint4* p = (const uint4*)(uintptr_t)(addr - r);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const uint4 v = p[q];
+    const uint4 v = lc_ok((uint64_t)(uintptr_t)(p + q), 16, kSiteMd5Granules) ? p[q] : make_uint4(0, 0, 0, 0);
     g[4 * q] = v.x, g[4 * q + 1] = v.y, g[4 * q + 2] = v.z, g[4 * q + 3] = v.w;
   }
   uint4 last = make_uint4(0, 0, 0, 0);
-  if (r) last = p[4];
+  if (r && lc_ok((uint64_t)(uintptr_t)(p + 4), 16, kSiteMd5Granules)) last = p[4];
   g[16] = last.x, g[17] = last.y, g[18] = last.z, g[19] = last.w;
 }
 
@@ -274,7 +275,8 @@ __global__ __launch_bounds__(64) void k_md5_hash(const hf3fs_crc_md5_seg* __rest
           const uint32_t jn = (uint32_t)__shfl((int)granules, j, 64);
           if (c < jn) {
             const uint4* p = (const uint4*)(uintptr_t)(((uint64_t)a_hi << 32) | a_lo);
-            rows[(uint32_t)j * kRowGranules + c] = p[c];
+            rows[(uint32_t)j * kRowGranules + c] =
+                lc_ok((uint64_t)(uintptr_t)(p + c), 16, kSiteMd5StageRow) ? p[c] : make_uint4(0, 0, 0, 0);
           }
         }
       }

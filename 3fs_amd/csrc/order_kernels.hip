@@ -1,6 +1,7 @@
 // order_kernels.hip -- see order_kernels.h.  These kernels only move 56-byte records and 4-byte
 // indices; the bytes are hashed and written by the update pipeline between the steps.
 #include "order_kernels.h"
+#include "loadcheck.h"
 
 namespace hf3fs_crc {
 namespace {
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void k_order_insert(const hf3fs_crc_update_io*
                                                       const uint32_t shift) {
   const uint32_t mask = table - 1;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const unsigned long long key = ios[i].chunk;
+    const unsigned long long key = HF3FS_LC_REC(ios, i, n).chunk;
     uint32_t at = kOrderNone, link = kOrderNone;
     if (key) {  // (chunk 0 stays a chain of its own: rank 0, it fails or not as in update_batch)
       uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift) & mask;
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(256) void k_order_step(hf3fs_crc_update_io* __restr
       ios[i].status = o.status;
       const uint32_t j = succ[i];
       if (!last && j != kOrderNone && j < n) {
-        hf3fs_crc_update_io nx = ios[j];
+        hf3fs_crc_update_io nx = HF3FS_LC_REC(ios, j, n);
         nx.chunk_size = o.out_size;
         nx.chunk_checksum_type = o.out_checksum_type;
         nx.chunk_checksum = o.out_checksum;
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void k_order_step(hf3fs_crc_update_io* __restr
       if (ri != r)
         round[i] = hf3fs_crc_update_io{};
       else if (r == 0)
-        round[i] = ios[i];
+        round[i] = HF3FS_LC_REC(ios, i, n);
     } else if (ri >= max_rounds) {
       uint32_t p = pred[i];
       for (uint64_t steps = 0; steps < n && p < n && rank[p] >= max_rounds; ++steps) p = pred[p];

@@ -98,10 +98,10 @@ __device__ __forceinline__ uint8_t ck_case(const hf3fs_crc_update_io& io, const 
 // dst (hf3fs_crc_update_cow_batch's d_dst[i], 0 = in place): the IO's new image is written at
 // plan_image(io.chunk, dst).  The pre jobs still read io.chunk (DELTA's old bytes are the
 // committed version's); the post jobs read the new image.
-__device__ __forceinline__ Eff prep_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i, uint32_t max_len,
+__device__ __forceinline__ Eff prep_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i HF3FS_LC_N(n), uint32_t max_len,
                                         uint8_t type, int mode, const UpdateScratch& s, uint32_t& pre_max,
                                         uint32_t& post_max, uint64_t dst = 0) {
-  const hf3fs_crc_update_io io = ios[i];
+  const hf3fs_crc_update_io io = HF3FS_LC_REC(ios, i, n);
   const Eff e = derive(io, max_len, type, mode);
   // only the output fields are stored: the prep launch's runs workgroup reads the input
   // fields of the same records meanwhile (bal_runs_block), so they are never rewritten
@@ -155,7 +155,7 @@ __device__ __forceinline__ void bal_runs_block(const hf3fs_crc_update_io* __rest
   hf3fs_crc_update_io io[kRunIos];
 #pragma unroll
   for (uint32_t u = 0; u < kRunIos; ++u)
-    if (i0 + u < n) io[u] = ios[i0 + u];
+    if (i0 + u < n) io[u] = HF3FS_LC_REC(ios, i0 + u, n);
   uint64_t l[2 * kRunIos];
   uint64_t mine = 0;
 #pragma unroll
@@ -252,9 +252,9 @@ __global__ __launch_bounds__(kPrepThreads) void k_update_prep(hf3fs_crc_update_i
     PlanRange R[kPlanRanges] = {};
     uint32_t wval = 0, verify = 0, pre_max = 0, post_max = 0;
     if (i < n) {
-      const hf3fs_crc_update_io io = ios[i];
-      const uint64_t dst = RPI == 2 || !dsts ? 0 : dsts[i];
-      const Eff e = prep_one(ios, i, max_len, type, mode, s, pre_max, post_max, dst);
+      const hf3fs_crc_update_io io = HF3FS_LC_REC(ios, i, n);
+      const uint64_t dst = RPI == 2 || !dsts ? 0 : (lc_desc_ok(i, n) ? dsts[i] : 0);
+      const Eff e = prep_one(ios, i HF3FS_LC_PASS(n), max_len, type, mode, s, pre_max, post_max, dst);
       plan_ranges(io, e, plan_image(io.chunk, dst), R);
       if (e.ok) {
         wval = e.wval;
@@ -401,7 +401,7 @@ __device__ void copy_range(uint64_t dst, uint64_t src, uint64_t len, uint32_t ti
     const uint64_t nh = hend - d0, nt = d1 - tstart;
     if (tid < nh + nt) {
       const uint64_t b = tid < nh ? d0 + tid : tstart + (tid - nh);
-      *reinterpret_cast<uint8_t*>(b) = src ? *reinterpret_cast<const uint8_t*>(src + (b - d0)) : 0;
+      *reinterpret_cast<uint8_t*>(b) = src ? load_byte(src + (b - d0), kSiteCopyByte) : 0;
     }
   }
   if (glast <= gfirst) return;
@@ -448,6 +448,7 @@ typedef unsigned int u32x4u __attribute__((ext_vector_type(4), aligned(1)));
 typedef __attribute__((address_space(1))) const u32x4u g_cu32x4u;
 template <bool NT>
 __device__ __forceinline__ u32x4 ldu16(uint64_t a) {
+  if (!lc_ok(a, 16, kSiteLdu16)) return u32x4{0, 0, 0, 0};
   if (NT) return __builtin_nontemporal_load(reinterpret_cast<g_cu32x4u*>(a));
   return *reinterpret_cast<g_cu32x4u*>(a);
 }
@@ -463,7 +464,7 @@ __device__ void copy_range_hw(uint64_t dst, uint64_t src, uint64_t len, uint32_t
     const uint64_t nh = hend - d0, nt = d1 - tstart;
     if (tid < nh + nt) {
       const uint64_t b = tid < nh ? d0 + tid : tstart + (tid - nh);
-      *reinterpret_cast<uint8_t*>(b) = src ? *reinterpret_cast<const uint8_t*>(src + (b - d0)) : 0;
+      *reinterpret_cast<uint8_t*>(b) = src ? load_byte(src + (b - d0), kSiteCopyByte) : 0;
     }
   }
   if (glast <= gfirst) return;
@@ -502,10 +503,10 @@ __device__ void copy_range_hw(uint64_t dst, uint64_t src, uint64_t len, uint32_t
 // Writes only the output fields: the apply kernel runs this beside copies that never
 // read them.
 template <class M>
-__device__ __forceinline__ void finalize_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i, uint8_t type,
+__device__ __forceinline__ void finalize_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i HF3FS_LC_N(n), uint8_t type,
                                              int mode, const UpdateScratch& s, const M& g, uint32_t max_len,
                                              int which) {
-  const hf3fs_crc_update_io io = ios[i];
+  const hf3fs_crc_update_io io = HF3FS_LC_REC(ios, i, n);
   if (io.status != HF3FS_CRC_OK) return;
   const Eff e = derive(io, max_len, type, mode);
   const bool post = e.kase == 4 && !e.delta;
@@ -564,12 +565,12 @@ __device__ __forceinline__ void finalize_one(hf3fs_crc_update_io* __restrict__ i
 // xor-ed across the wave.
 __device__ uint32_t lin_serial(uint64_t a, uint64_t b, const ShortTables* __restrict__ S) {
   uint32_t c = 0;
-  for (; a < b && (a & 3); ++a) c = (c >> 8) ^ S->b8[(c ^ *reinterpret_cast<const uint8_t*>(a)) & 0xffu];
+  for (; a < b && (a & 3); ++a) c = (c >> 8) ^ S->b8[(c ^ load_byte(a, kSiteAuditBytes)) & 0xffu];
   for (; a + 4 <= b; a += 4) {
-    c ^= *reinterpret_cast<const uint32_t*>(a);
+    c ^= lc_ok(a, 4, kSiteAuditBytes) ? *reinterpret_cast<const uint32_t*>(a) : 0u;
     c = S->dw[0][c & 0xffu] ^ S->dw[1][(c >> 8) & 0xffu] ^ S->dw[2][(c >> 16) & 0xffu] ^ S->dw[3][c >> 24];
   }
-  for (; a < b; ++a) c = (c >> 8) ^ S->b8[(c ^ *reinterpret_cast<const uint8_t*>(a)) & 0xffu];
+  for (; a < b; ++a) c = (c >> 8) ^ S->b8[(c ^ load_byte(a, kSiteAuditBytes)) & 0xffu];
   return c;
 }
 
@@ -591,10 +592,10 @@ __device__ uint64_t runs_cover(const UpdateScratch& s, uint64_t j, uint64_t L, u
 
 // IO i was finalized with HF3FS_CRC_CHECKSUM_MISMATCH; the whole wave re-checks it.
 template <uint32_t POLY>
-__device__ void audit_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i, uint8_t type, int mode,
+__device__ void audit_one(hf3fs_crc_update_io* __restrict__ ios, uint64_t i HF3FS_LC_N(n), uint8_t type, int mode,
                           const UpdateScratch& s, const PolyTables* __restrict__ T,
                           const ShortTables* __restrict__ S, uint32_t max_len, uint32_t lane) {
-  const hf3fs_crc_update_io io = ios[i];
+  const hf3fs_crc_update_io io = HF3FS_LC_REC(ios, i, n);
   const Eff e = derive(io, max_len, type, mode);
   if (!e.verify) return;  // (a mismatch status comes only from the verify)
   const uint64_t L = e.len, p = io.payload;
@@ -677,7 +678,7 @@ __device__ __forceinline__ void one_shot_piece(uint64_t b, uint32_t r, const App
     bb = tid < nh ? a + tid : ge + (tid - nh);
   }
   typedef __attribute__((address_space(1))) uint8_t g_u8;  // global, not flat: vmcnt only
-  const uint8_t x = byte && R.src ? *reinterpret_cast<const g_u8*>(bb + so) : 0;
+  const uint8_t x = byte && R.src && lc_ok(bb + so, 1, kSiteApplyByte) ? *reinterpret_cast<const g_u8*>(bb + so) : 0;
   const uint64_t ng = ge > ga ? (ge - ga) >> 4 : 0;
   // the first granule is loaded beside the verdict; each later one after the previous store
   // (load -> store per granule measured faster than all loads first: a wave keeps less in
@@ -731,7 +732,7 @@ __global__ __launch_bounds__(256) void k_update_apply(hf3fs_crc_update_io* __res
   // loop's register count and cost 85 us per d3 batch in occupancy)
   if (fin)
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-      finalize_one(ios, i, type, mode, s, GfGlobal<POLY>{T}, max_len, 1);
+      finalize_one(ios, i HF3FS_LC_PASS(n), type, mode, s, GfGlobal<POLY>{T}, max_len, 1);
   const uint64_t ntasks = *reinterpret_cast<const uint64_t*>(s.ctl + kCtlTasks);
   if (hint && blockIdx.x == 0 && threadIdx.x == 0)
     store_hint(hint, *reinterpret_cast<const uint64_t*>(s.ctl + kCtlPieces), n);
@@ -767,10 +768,10 @@ __global__ __launch_bounds__(kThreads) void k_update_fused(hf3fs_crc_update_io* 
   while (i < n) {
     if (threadIdx.x == 0) {
       uint32_t pre_max, post_max;
-      const Eff e = prep_one(ios, i, max_len, type, mode, s, pre_max, post_max);
+      const Eff e = prep_one(ios, i HF3FS_LC_PASS(n), max_len, type, mode, s, pre_max, post_max);
       if (pre_max) atomicMax(&s.ctl[kCtlPreMax], pre_max);
       if (post_max) atomicMax(&s.ctl[kCtlPostMax], post_max);
-      const hf3fs_crc_update_io& io = ios[i];
+      const hf3fs_crc_update_io& io = HF3FS_LC_REC(ios, i, n);
       s_chunk = io.chunk;
       s_pay = io.payload;
       s_job[0] = e.ok;
@@ -848,14 +849,14 @@ __global__ __launch_bounds__(256) void k_update_finalize(hf3fs_crc_update_io* __
     const uint64_t i = i0 + lane;
     bool flag = false;
     if (i < n) {
-      finalize_one(ios, i, type, mode, s, g, max_len, which);
+      finalize_one(ios, i HF3FS_LC_PASS(n), type, mode, s, g, max_len, which);
       flag = audit && ios[i].status == HF3FS_CRC_CHECKSUM_MISMATCH;
     }
     uint64_t m = __ballot(flag);
     while (m) {  // wave-uniform
       const int bit = __ffsll((unsigned long long)m) - 1;
       m &= m - 1;
-      audit_one<POLY>(ios, i0 + bit, type, mode, s, T, S, max_len, lane);
+      audit_one<POLY>(ios, i0 + bit HF3FS_LC_PASS(n), type, mode, s, T, S, max_len, lane);
     }
   }
 }
@@ -874,7 +875,7 @@ __device__ __forceinline__ bool read_full(const hf3fs_crc_read_io& io) {
 __global__ void k_read_prep(hf3fs_crc_read_io* __restrict__ ios, uint64_t n, uint8_t type, uint32_t max_len,
                             uint64_t* __restrict__ addr, uint64_t* __restrict__ len, uint32_t* __restrict__ maxl) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    hf3fs_crc_read_io io = ios[i];
+    hf3fs_crc_read_io io = HF3FS_LC_REC(ios, i, n);
     const bool full = read_full(io);
     const bool reuse = io.batch_checksum_type == io.chunk_checksum_type && full;                       // :30-31
     const bool create = io.batch_checksum_type != kTypeNone && !reuse;                                   // :32-35
@@ -895,7 +896,7 @@ __global__ void k_read_prep(hf3fs_crc_read_io* __restrict__ ios, uint64_t n, uin
 
 __global__ void k_read_finalize(hf3fs_crc_read_io* __restrict__ ios, uint64_t n, const uint32_t* __restrict__ v) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    hf3fs_crc_read_io io = ios[i];
+    hf3fs_crc_read_io io = HF3FS_LC_REC(ios, i, n);
     if (io.status != HF3FS_CRC_OK) continue;
     const bool full = read_full(io);
     if (io.batch_checksum_type == kTypeNone) {

@@ -1,6 +1,7 @@
 // version_kernels.hip -- see version_kernels.h.  Like the order kernels these only move records
 // and indices; the bytes are hashed and written by the update pipeline between the steps.
 #include "version_kernels.h"
+#include "loadcheck.h"
 
 #include "update_plan.h"
 #include "version_plan.h"
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void k_version_step(const StepArgs a) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t ri = a.rank[i];
     if (a.r > 0 && ri == a.r - 1) {
-      const hf3fs_crc_update_ver v = a.ver[i];
+      const hf3fs_crc_update_ver v = HF3FS_LC_REC(a.ver, i, a.n);
       uint32_t size, cval;
       uint8_t ctype;
       VerState after = load_out(v);
@@ -115,19 +116,19 @@ __global__ __launch_bounds__(256) void k_version_step(const StepArgs a) {
         }
         size = o.out_size, ctype = o.out_checksum_type, cval = o.out_checksum;
       } else {  // decided in the step before its round: nothing of it is rewritten here
-        const hf3fs_crc_update_io me = a.ios[i];
+        const hf3fs_crc_update_io me = HF3FS_LC_REC(a.ios, i, a.n);
         size = me.chunk_size, ctype = me.chunk_checksum_type, cval = me.chunk_checksum;
       }
       const uint32_t j = a.succ[i];
       if (!last && j != kOrderNone && j < n) {
-        hf3fs_crc_update_io nx = a.ios[j];
+        hf3fs_crc_update_io nx = HF3FS_LC_REC(a.ios, j, a.n);
         nx.chunk_size = size;
         nx.chunk_checksum_type = ctype;
         nx.chunk_checksum = cval;
         a.ios[j].chunk_size = size;
         a.ios[j].chunk_checksum_type = ctype;
         a.ios[j].chunk_checksum = cval;
-        hf3fs_crc_update_ver nv = a.ver[j];
+        hf3fs_crc_update_ver nv = HF3FS_LC_REC(a.ver, j, a.n);
         store_before(&nv, after);
         store_before(&a.ver[j], after);
         decide(a, j, nx, nv);
@@ -143,19 +144,19 @@ __global__ __launch_bounds__(256) void k_version_step(const StepArgs a) {
           a.vlen[i] = 0;
         }
       } else if (a.r == 0) {
-        decide(a, (uint32_t)i, a.ios[i], a.ver[i]);
+        decide(a, (uint32_t)i, HF3FS_LC_REC(a.ios, i, a.n), HF3FS_LC_REC(a.ver, i, a.n));
       }
     } else if (ri >= a.max_rounds) {
       uint32_t p = a.pred[i];
       for (uint64_t steps = 0; steps < n && p < n && a.rank[p] >= a.max_rounds; ++steps) p = a.pred[p];
-      hf3fs_crc_update_ver mine = a.ver[i];
+      hf3fs_crc_update_ver mine = HF3FS_LC_REC(a.ver, i, a.n);
       VerState st = ver_before(mine);
       if (p < n) {
-        const hf3fs_crc_update_ver pv = a.ver[p];
+        const hf3fs_crc_update_ver pv = HF3FS_LC_REC(a.ver, p, a.n);
         // (input fields of ios[p] only: its thread is writing the outputs)
-        uint32_t size = a.ios[p].chunk_size, cval = a.ios[p].chunk_checksum;
-        uint8_t ctype = a.ios[p].chunk_checksum_type;
-        const uint8_t pflags = a.ios[p].flags;
+        uint32_t size = HF3FS_LC_REC(a.ios, p, a.n).chunk_size, cval = HF3FS_LC_REC(a.ios, p, a.n).chunk_checksum;
+        uint8_t ctype = HF3FS_LC_REC(a.ios, p, a.n).chunk_checksum_type;
+        const uint8_t pflags = HF3FS_LC_REC(a.ios, p, a.n).flags;
         if (a.dec[p] == 0u) {
           const hf3fs_crc_update_io o = a.round[p];
           size = o.out_size, ctype = o.out_checksum_type, cval = o.out_checksum;
@@ -197,13 +198,13 @@ __global__ __launch_bounds__(256) void k_version_settle(hf3fs_crc_update_io* __r
     uint32_t kind = 0;  // bit per info word 2..7
     if (i < n && rank[i] < max_rounds) {
       const uint32_t d = dec[i];
-      int32_t status = ios[i].status;
+      int32_t status = HF3FS_LC_REC(ios, i, n).status;
       if (((d >> kDecWhereShift) & 0xffu) == kVerLate) {
         status = (int32_t)(d & kDecStatusMask);
-        if ((d & kDecVerifyBit) && vout[i] != ios[i].write_checksum) status = HF3FS_CRC_CHECKSUM_MISMATCH;
+        if ((d & kDecVerifyBit) && vout[i] != HF3FS_LC_REC(ios, i, n).write_checksum) status = HF3FS_CRC_CHECKSUM_MISMATCH;
         ios[i].status = status;
       }
-      const bool commit = ios[i].update_type == HF3FS_UPDATE_COMMIT;
+      const bool commit = HF3FS_LC_REC(ios, i, n).update_type == HF3FS_UPDATE_COMMIT;
       if (status == HF3FS_CRC_OK) {
         kind = commit ? 2u : 1u;
       } else {
