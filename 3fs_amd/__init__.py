@@ -27,4 +27,8 @@ from ._lib import (ENGINE_INFO_NAMES, ENGINE_INFO_WORDS, engine_job_dtype, updat
                    update_engine_scratch_bytes)
 from ._lib import (MD5_FINAL, MD5_INIT, md5_batch, md5_hex, md5_scratch_bytes, md5_seg_dtype,  # noqa: F401
                    md5_state_dtype)
+from ._lib import (CHUNK_NOT_FOUND, CLIENT_NOT_INITIALIZED, CLIENT_READ_INFO_NAMES,  # noqa: F401
+                   CLIENT_READ_INFO_WORDS, CLIENT_READ_NONE, CLIENT_READ_VERIFY, ClientReadIO, ClientReadResult,
+                   block_digest_dtype, client_read_batch, client_read_io_dtype, client_read_result_dtype,
+                   client_read_scratch_bytes)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

@@ -144,6 +144,43 @@ class FileDigest(ctypes.Structure):
 
 assert ctypes.sizeof(BlockDigest) == 24 and ctypes.sizeof(FileDigest) == 24
 
+
+class ClientReadIO(ctypes.Structure):
+    """hf3fs_crc_client_read_io: one ReadIO of a completed batchRead (StorageClientImpl.cc:1720-1737)."""
+    _fields_ = [
+        ("data", ctypes.c_uint64),
+        ("length", ctypes.c_uint32),
+        ("read_len", ctypes.c_uint32),
+        ("status_in", ctypes.c_int32),
+        ("checksum", ctypes.c_uint32),
+        ("checksum_type", ctypes.c_uint8),
+        ("reserved0", ctypes.c_uint8 * 3),
+        ("computed", ctypes.c_uint32),
+        ("status", ctypes.c_int32),
+        ("reserved1", ctypes.c_uint32),
+    ]
+
+
+class ClientReadResult(ctypes.Structure):
+    """hf3fs_crc_client_read_result: parentIO->result after the merge (StorageClientImpl.cc:1607-1633)."""
+    _fields_ = [
+        ("length", ctypes.c_uint32),
+        ("checksum", ctypes.c_uint32),
+        ("checksum_type", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 3),
+        ("status", ctypes.c_int32),
+        ("failed_child", ctypes.c_uint32),
+        ("block_len", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(ClientReadIO) == 40 and ctypes.sizeof(ClientReadResult) == 24
+CLIENT_READ_VERIFY = 1  # hf3fs_crc_client_read_batch flags
+CLIENT_NOT_INITIALIZED, CHUNK_NOT_FOUND = 7003, 7007
+CLIENT_READ_INFO_WORDS = 4
+CLIENT_READ_INFO_NAMES = ("bad_children", "bad_parents", "hard_parents", "reserved")
+CLIENT_READ_NONE = 0xFFFFFFFF  # ClientReadResult.failed_child: no child took over
+
 class ScrubIO(ctypes.Structure):
     """hf3fs_crc_scrub_io: one stored chunk vs its persisted checksum."""
     _fields_ = [
@@ -299,6 +336,8 @@ SIGNATURES = {
     "hf3fs_crc_update_cow_scratch_bytes": (ctypes.c_size_t, [_u64, _u32, _int]),
     "hf3fs_crc_pair_scratch_stats": (_int, [_vp, _vp, _vp]),
     "hf3fs_crc_read_result_batch": (_int, [_u8, _vp, _u64, _u32, _vp]),
+    "hf3fs_crc_client_read_batch": (_int, [_u8, _vp, _u64, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "hf3fs_crc_client_read_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
     "hf3fs_crc_file_digest_batch": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "hf3fs_crc_file_digest_batch_ex": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
     "hf3fs_crc_md5_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp]),
@@ -549,6 +588,47 @@ def file_digest_batch(blocks, file_off, out, n_files, max_blocks, stream=None, f
     the admin command without --fill-zero (first missing / short block is the status)."""
     return check(load().hf3fs_crc_file_digest_batch_ex(_p(blocks), _p(file_off), _p(out), n_files, max_blocks,
                                                        DIGEST_FILL_ZERO if fill_zero else 0, _s(stream)))
+
+
+def client_read_io_dtype():
+    """numpy dtype of hf3fs_crc_client_read_io (include/hf3fs_crc.h): one 40-byte record per IO."""
+    import numpy as np
+    return np.dtype([("data", "<u8"), ("length", "<u4"), ("read_len", "<u4"), ("status_in", "<i4"),
+                     ("checksum", "<u4"), ("checksum_type", "u1"), ("reserved0", "u1", (3,)), ("computed", "<u4"),
+                     ("status", "<i4"), ("reserved1", "<u4")])
+
+
+def client_read_result_dtype():
+    """numpy dtype of hf3fs_crc_client_read_result: one 24-byte record per parent."""
+    import numpy as np
+    return np.dtype([("length", "<u4"), ("checksum", "<u4"), ("checksum_type", "u1"), ("reserved", "u1", (3,)),
+                     ("status", "<i4"), ("failed_child", "<u4"), ("block_len", "<u4")])
+
+
+def block_digest_dtype():
+    """numpy dtype of hf3fs_crc_block_digest: what client_read_batch hands to file_digest_batch."""
+    import numpy as np
+    return np.dtype([("read_len", "<u8"), ("block_len", "<u8"), ("checksum", "<u4"), ("checksum_type", "u1"),
+                     ("missing", "u1"), ("reserved", "u1", (2,))])
+
+
+def client_read_batch(ctype, ios, n_ios, info, parent_off=None, n_parents=None, max_children=1, max_len=0,
+                      verify=True, parents=None, blocks=None, flags=None, stream=None):
+    """hf3fs_crc_client_read_batch: ios a device array of hf3fs_crc_client_read_io (computed and
+    status updated in place), parent_off n_parents + 1 device uint64 or None (every IO its own
+    parent), parents / blocks device arrays of hf3fs_crc_client_read_result / hf3fs_crc_block_digest
+    (either may be None), info CLIENT_READ_INFO_WORDS device u32.  flags overrides verify."""
+    if n_parents is None:
+        n_parents = n_ios
+    if flags is None:
+        flags = CLIENT_READ_VERIFY if verify else 0
+    return check(load().hf3fs_crc_client_read_batch(ctype, _p(ios), n_ios, _p(parent_off), n_parents, max_children,
+                                                    max_len, flags, _p(parents), _p(blocks), _p(info), _s(stream)))
+
+
+def client_read_scratch_bytes(n_ios, n_parents):
+    """Bytes of library-owned scratch one verifying client_read_batch takes (0: rejected counts)."""
+    return int(load().hf3fs_crc_client_read_scratch_bytes(n_ios, n_parents))
 
 
 MD5_INIT, MD5_FINAL = 1, 2  # hf3fs_crc_md5_batch flags

@@ -22,6 +22,8 @@
 #include "../../include/hf3fs_crc.h"
 #include "aux_kernels.h"
 #include "capture_scratch.h"
+#include "client_read_kernels.h"
+#include "client_read_plan.h"  // kClientMaxCount
 #include "frame_kernels.h"
 #include "crc_kernels.h"
 #include "digest_kernels.h"
@@ -37,6 +39,8 @@
 
 static_assert(sizeof(hf3fs_crc_update_io) == 56, "hf3fs_crc_update_io ABI layout");
 static_assert(sizeof(hf3fs_crc_read_io) == 48, "hf3fs_crc_read_io ABI layout");
+static_assert(sizeof(hf3fs_crc_client_read_io) == 40 && sizeof(hf3fs_crc_client_read_result) == 24,
+              "hf3fs_crc_client_read_io / _result ABI layout");
 static_assert(sizeof(hf3fs_crc_block_digest) == 24, "hf3fs_crc_block_digest ABI layout");
 static_assert(sizeof(hf3fs_crc_file_digest) == 24, "hf3fs_crc_file_digest ABI layout");
 static_assert(sizeof(hf3fs_crc_scrub_io) == 32, "hf3fs_crc_scrub_io ABI layout");
@@ -1279,6 +1283,52 @@ int hf3fs_crc_read_result_batch(uint8_t type, hf3fs_crc_read_io* d_ios, uint64_t
         return launch_read_prep(d_ios, n, type, max_len, addr, len, maxl, s);
       },
       [&](const uint32_t* v) { return launch_read_finalize(d_ios, n, v, s); }, "read");
+}
+
+size_t hf3fs_crc_client_read_scratch_bytes(uint64_t n_ios, uint64_t n_parents) {
+  if (n_ios > kClientMaxCount || n_parents > kClientMaxCount) return 0;
+  // run_record_jobs' carve {maxl[4], addr[n], len[n], v[n]}, as the pair's buffer is sized by a
+  // first call (a captured call's own memory is the exact bytes); the parents take no scratch.
+  const size_t bytes = (16 + (size_t)n_ios * (8 + 8 + 4) + 63) / 64 * 64 + 64;
+  return roomy_words((bytes + 3) / 4) * 4;
+}
+
+int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io* d_ios, uint64_t n_ios,
+                                const uint64_t* d_parent_off, uint64_t n_parents, uint64_t max_children,
+                                uint32_t max_len, uint32_t flags, hf3fs_crc_client_read_result* d_parents,
+                                hf3fs_crc_block_digest* d_blocks, uint32_t* d_info, void* stream) {
+  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (flags & ~(uint32_t)HF3FS_CLIENT_READ_VERIFY) return fail(HF3FS_CRC_INVALID_ARG, "unknown flags %#x", flags);
+  if (!d_ios && n_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if (!d_parent_off && n_parents != n_ios)
+    return fail(HF3FS_CRC_INVALID_ARG, "null parent offsets need n_parents == n_ios (%llu != %llu)",
+                (unsigned long long)n_parents, (unsigned long long)n_ios);
+  const bool verify = (flags & HF3FS_CLIENT_READ_VERIFY) != 0;
+  if (!d_parents && !d_blocks && !verify) return fail(HF3FS_CRC_INVALID_ARG, "nothing to do: no output and no VERIFY");
+  if (n_ios > kClientMaxCount || n_parents > kClientMaxCount)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many IOs or parents (%llu, %llu)", (unsigned long long)n_ios,
+                (unsigned long long)n_parents);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_CLIENT_READ_INFO_WORDS, s));  // the merge adds into it
+  if (n_ios == 0 && n_parents == 0) return HF3FS_CRC_OK;
+  const bool wave = max_children > kClientLaneMaxChildren;
+  const auto merge = [&](const uint32_t* v) {
+    return launch_client_read_merge(d_ios, n_ios, d_parent_off, n_parents, type, max_len, v != nullptr, wave, v,
+                                    d_parents, d_blocks, d_info, c->tables, s);
+  };
+  if (!verify || n_ios == 0) {  // no child is compared: no byte is read, no scratch taken
+    HIP_OR_FAIL(merge(nullptr));
+    return HF3FS_CRC_OK;
+  }
+  return run_record_jobs(
+      c, type, n_ios, max_len, ~0u, s,
+      [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
+        return launch_client_read_prep(d_ios, n_ios, type, max_len, addr, len, maxl, s);
+      },
+      merge, "client read");
 }
 
 int hf3fs_crc_scrub_batch(uint8_t type, hf3fs_crc_scrub_io* d_ios, uint64_t n, uint32_t max_len,

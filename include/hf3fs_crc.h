@@ -688,6 +688,96 @@ int hf3fs_crc_file_digest_batch_ex(const hf3fs_crc_block_digest *d_blocks, const
                                    uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* client batchRead completion: the verify ladder and the split-read merge    */
+/* ------------------------------------------------------------------------ */
+/* One ReadIO as StorageClientImpl::batchRead sent it: a split child, or an unsplit IO
+ * (src/client/storage/StorageClientImpl.cc:1720-1737 reads these fields). */
+typedef struct hf3fs_crc_client_read_io {
+  uint64_t data;          /* device address of readIO->data (read with VERIFY only) */
+  uint32_t length;        /* ReadIO.length (requested) */
+  uint32_t read_len;      /* *result.lengthInfo when status_in == 0 */
+  int32_t status_in;      /* 0: lengthInfo holds a value; else result.lengthInfo.error().code() */
+  uint32_t checksum;      /* result.checksum.value as the server sent it (raw) */
+  uint8_t checksum_type;  /* result.checksum.type */
+  uint8_t reserved0[3];
+  /* outputs */
+  uint32_t computed;      /* the local ChecksumInfo::create value when the IO was hashed, else 0 */
+  int32_t status;         /* result after the verify: status_in, 7015 on mismatch, 3 for a bad record */
+  uint32_t reserved1;
+} hf3fs_crc_client_read_io;
+
+/* parentIO->result after the merge loop (StorageClientImpl.cc:1607-1633). */
+typedef struct hf3fs_crc_client_read_result {
+  uint32_t length;        /* lengthInfo value (mod 2^32, as the reference sums it, :1629); 0 when status != 0 */
+  uint32_t checksum;
+  uint8_t checksum_type;
+  uint8_t reserved[3];
+  int32_t status;         /* 0, or the taking-over child's status; 7003 for a parent without children */
+  uint32_t failed_child;  /* index in d_ios of the child that took over, ~0u if none */
+  uint32_t block_len;     /* sum of the children's `length` (mod 2^32) */
+} hf3fs_crc_client_read_result;
+
+enum { HF3FS_CRC_CLIENT_NOT_INITIALIZED = 7003 }; /* StorageClientCode::kNotInitialized (:224): IOResult's default */
+enum { HF3FS_CLIENT_READ_VERIFY = 1 };            /* flags: options.verifyChecksum() (:1720) */
+enum {                                            /* words of d_info */
+  HF3FS_CLIENT_READ_INFO_BAD_CHILDREN = 0,        /* children whose status after the verify is not 0 */
+  HF3FS_CLIENT_READ_INFO_BAD_PARENTS = 1,         /* parents whose status is not 0 */
+  HF3FS_CLIENT_READ_INFO_HARD_PARENTS = 2,        /* parents whose status is not in {0, 7007}: an error a
+                                                     block record cannot express */
+  HF3FS_CLIENT_READ_INFO_WORDS = 4                /* (word 3 is written as 0) */
+};
+
+/* What the client does with a completed batchRead, for n_ios IOs and n_parents parents, on the
+ * device and without a host round trip between the two steps.
+ *
+ * Verify (StorageClientImpl.cc:1720-1737), with HF3FS_CLIENT_READ_VERIFY only: a child with
+ * status_in == 0 and read_len > 0 (:1722) is hashed in the type the server answered with (:1723);
+ * a NONE-typed child computes {NONE, 0} without reading a byte (Common.h:150), so it mismatches
+ * exactly when the server's value is not 0.  A mismatch (:1726) makes the child's result
+ * IOResult(7015) (:1733): status 7015, and for the merge its checksum is {NONE, 0}.  Bad records
+ * get status 3 and are not hashed: a child with status_in == 0 whose type is unknown (> CRC32)
+ * or, with VERIFY, neither NONE nor `type` (the rule of hf3fs_crc_read_result_batch), or, with
+ * VERIFY, whose read_len exceeds max_len or its own `length`, or whose data is 0 with
+ * read_len > 0.  Every child gets `computed` and `status`.  Without VERIFY no data byte is read
+ * and `data` may be anything; both CRC types may then occur in one batch.
+ *
+ * Merge (:1607-1633): parent p owns children [d_parent_off[p], d_parent_off[p+1]) of d_ios
+ * (offsets ascending, the last one n_ios; an offset past n_ios is clamped); a null d_parent_off
+ * means every IO is its own parent and needs n_parents == n_ios.  The first child whose status
+ * after the verify is not 0 takes over (:1621-1623): the parent gets its status and its checksum
+ * fields (those of IOResult(7015) after a mismatch), length 0, and failed_child.  Otherwise child
+ * 0 is assigned (:1625); each later child adds its read_len in uint32_t (:1629) and is combined
+ * (:1630) by ChecksumInfo::combine (src/fbs/storage/Common.h:179-198) with the return value
+ * dropped: a parent typed otherwise than the child stays as it is (:180-183, the length was
+ * added already), read_len 0 changes nothing (:184), a NONE parent adopts the child's checksum
+ * (:186-188), else the CRC combine (:190-196).  A parent without children keeps IOResult's
+ * default: status 7003, {NONE, 0}.
+ *
+ * d_blocks[p], when given, is the record FileWrapper::readFile builds from the parent
+ * (src/client/cli/admin/FileWrapper.cc:132-163) and hf3fs_crc_file_digest_batch_ex takes:
+ * read_len = length, block_len, checksum, checksum_type, missing = (status == 7007).
+ * d_info[HF3FS_CLIENT_READ_INFO_*] is set, not accumulated.  d_parents or d_blocks may be NULL,
+ * both with VERIFY: the parents are merged all the same and d_info counts them in every mode.
+ *
+ * HF3FS_CRC_INVALID_ARG before a device is touched: a type other than CRC32C / CRC32, unknown
+ * flag bits, null d_ios with n_ios > 0, null d_info, null d_parent_off with n_parents != n_ios,
+ * d_parents and d_blocks both null without VERIFY, a count above 2^30.  n_ios == 0 with
+ * n_parents == 0 only zeroes d_info.  max_children >= every parent's child count chooses the
+ * schedule (one lane or one wave per parent); a parent with more children is still merged
+ * correctly.  max_len >= every read_len that is hashed.
+ *
+ * Asynchronous on `stream`, no host synchronisation, nothing read back; capturable, also as the
+ * process's first library call, and a replayed graph works from what the records hold at replay
+ * time.  No store goes to a caller data buffer. */
+int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io *d_ios, uint64_t n_ios,
+                                const uint64_t *d_parent_off, uint64_t n_parents, uint64_t max_children,
+                                uint32_t max_len, uint32_t flags, hf3fs_crc_client_read_result *d_parents,
+                                hf3fs_crc_block_digest *d_blocks, uint32_t *d_info, void *stream);
+/* Bytes of library-owned scratch one call of this shape takes with VERIFY (without it: none);
+ * 0 for rejected counts. */
+size_t hf3fs_crc_client_read_scratch_bytes(uint64_t n_ios, uint64_t n_parents);
+
+/* ------------------------------------------------------------------------ */
 /* file MD5: admin `checksum --md5`                                           */
 /* ------------------------------------------------------------------------ */
 /* One run of bytes of a file, in file order. data == 0: `length` zero bytes (a hole). */
