@@ -181,6 +181,53 @@ CLIENT_READ_INFO_WORDS = 4
 CLIENT_READ_INFO_NAMES = ("bad_children", "bad_parents", "hard_parents", "reserved")
 CLIENT_READ_NONE = 0xFFFFFFFF  # ClientReadResult.failed_child: no child took over
 
+
+_u8c, _u32c, _i32c, _u64c = ctypes.c_uint8, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64
+
+
+class ForwardJob(ctypes.Structure):
+    """hf3fs_crc_forward_job: one update between its local update and its commit
+    (StorageOperator.cc:401-485, ReliableForwarding.cc:113-278)."""
+    _fields_ = [
+        # request
+        ("payload", _u64c), ("chunk", _u64c), ("offset", _u32c), ("length", _u32c), ("chunk_size", _u32c),
+        ("req_update_ver", _u32c), ("req_checksum", _u32c), ("update_type", _u8c), ("req_checksum_type", _u8c),
+        ("req_flags", _u8c), ("upd_checksum_type", _u8c),
+        # local update result
+        ("upd_status", _i32c), ("upd_length", _u32c), ("upd_update_ver", _u32c), ("upd_commit_ver", _u32c),
+        ("upd_checksum", _u32c),
+        # target
+        ("chain_ver", _u32c), ("has_successor", _u8c), ("successor_syncing", _u8c), ("engine_job", _u8c),
+        ("chunk_checksum_type", _u8c),
+        # chunk
+        ("chunk_len", _u32c), ("chunk_checksum", _u32c), ("chunk_update_ver", _u32c),
+        ("chunk_commit_chain_ver", _u32c), ("chunk_status_in", _i32c),
+        # outputs of prepare
+        ("out_data", _u64c), ("status", _i32c), ("res_length", _u32c), ("res_update_ver", _u32c),
+        ("res_commit_ver", _u32c), ("out_offset", _u32c), ("out_length", _u32c), ("out_checksum", _u32c),
+        ("out_update_ver", _u32c), ("out_commit_chain_ver", _u32c), ("computed", _u32c), ("action", _u8c),
+        ("is_syncing", _u8c), ("out_update_type", _u8c), ("out_checksum_type", _u8c), ("out_flags", _u8c),
+        # the successor's response
+        ("fwd_checksum_type", _u8c), ("reserved0", _u8c * 2), ("fwd_status", _i32c), ("fwd_length", _u32c),
+        ("fwd_checksum", _u32c), ("fwd_commit_ver", _u32c), ("fwd_commit_chain_ver", _u32c),
+        # outputs of complete
+        ("final_status", _i32c), ("commit_ver", _u32c), ("commit_chain_ver", _u32c), ("fwd_update_ver", _u32c),
+        ("buffer_computed", _u32c), ("final_action", _u8c), ("buffer_corrupted", _u8c), ("reserved1", _u8c * 6),
+    ]
+
+
+assert ctypes.sizeof(ForwardJob) == 192
+UPDATE_REMOVE = 2  # hf3fs_crc_forward_job.update_type only
+NO_SUCCESSOR_TARGET = 4033
+FORWARD_REQ_SYNCING, FORWARD_REQ_INLINE = 1, 2
+FORWARD_OUT_SYNCING, FORWARD_OUT_INLINE, FORWARD_OUT_COMMIT_CHAIN_VER = 1, 2, 4
+FORWARD_RETURN, FORWARD_SEND, FORWARD_NO_SUCCESSOR, FORWARD_COMMIT = 1, 2, 3, 4
+FORWARD_INFO_WORDS = 8
+FORWARD_INFO_NAMES = ("sent", "returned", "no_successor", "sync_hashed", "sync_mismatched", "bad_records",
+                      "reserved6", "reserved7")
+FORWARD_DONE_NAMES = ("commits", "returned", "e7015", "e4081", "e4082", "rehashed", "corrupted", "unhashable")
+
+
 class ScrubIO(ctypes.Structure):
     """hf3fs_crc_scrub_io: one stored chunk vs its persisted checksum."""
     _fields_ = [
@@ -338,6 +385,9 @@ SIGNATURES = {
     "hf3fs_crc_read_result_batch": (_int, [_u8, _vp, _u64, _u32, _vp]),
     "hf3fs_crc_client_read_batch": (_int, [_u8, _vp, _u64, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
     "hf3fs_crc_client_read_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
+    "hf3fs_crc_forward_prepare": (_int, [_u8, _vp, _u64, _u32, _u32, _vp, _vp]),
+    "hf3fs_crc_forward_complete": (_int, [_u8, _vp, _u64, _u32, _vp, _vp, _vp]),
+    "hf3fs_crc_forward_scratch_bytes": (ctypes.c_size_t, [_u64]),
     "hf3fs_crc_file_digest_batch": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "hf3fs_crc_file_digest_batch_ex": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
     "hf3fs_crc_md5_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp]),
@@ -629,6 +679,33 @@ def client_read_batch(ctype, ios, n_ios, info, parent_off=None, n_parents=None, 
 def client_read_scratch_bytes(n_ios, n_parents):
     """Bytes of library-owned scratch one verifying client_read_batch takes (0: rejected counts)."""
     return int(load().hf3fs_crc_client_read_scratch_bytes(n_ios, n_parents))
+
+
+def forward_job_dtype():
+    """numpy dtype of hf3fs_crc_forward_job (include/hf3fs_crc.h): one 192-byte record per job."""
+    import numpy as np
+    kinds = {_u8c: "u1", _u32c: "<u4", _i32c: "<i4", _u64c: "<u8"}
+    return np.dtype([(name, kinds[t]) if t in kinds else (name, "u1", (ctypes.sizeof(t),))
+                     for name, t in ForwardJob._fields_])
+
+
+def forward_prepare(ctype, jobs, n, info, max_len, max_inline_bytes=0, stream=None):
+    """hf3fs_crc_forward_prepare: jobs a device array of hf3fs_crc_forward_job (the prepare outputs
+    written in place), info FORWARD_INFO_WORDS device u32."""
+    return check(load().hf3fs_crc_forward_prepare(ctype, _p(jobs), n, max_len, max_inline_bytes, _p(info),
+                                                  _s(stream)))
+
+
+def forward_complete(ctype, jobs, n, info, max_len, commit_idx=None, stream=None):
+    """hf3fs_crc_forward_complete: the complete outputs written in place, commit_idx n device u32 or
+    None (the COMMIT jobs' indices, ascending; their count is info[0])."""
+    return check(load().hf3fs_crc_forward_complete(ctype, _p(jobs), n, max_len, _p(commit_idx), _p(info),
+                                                   _s(stream)))
+
+
+def forward_scratch_bytes(n):
+    """Bytes of library-owned scratch either forward call takes for n jobs (0: rejected count)."""
+    return int(load().hf3fs_crc_forward_scratch_bytes(n))
 
 
 MD5_INIT, MD5_FINAL = 1, 2  # hf3fs_crc_md5_batch flags

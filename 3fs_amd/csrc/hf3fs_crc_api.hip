@@ -28,6 +28,8 @@
 #include "crc_kernels.h"
 #include "digest_kernels.h"
 #include "engine_kernels.h"
+#include "forward_kernels.h"
+#include "forward_plan.h"  // kForwardMaxJobs
 #include "internal.h"
 #include "md5_kernels.h"
 #include "options.h"
@@ -495,15 +497,20 @@ constexpr uint64_t kRunWindowBytes = 4ull << 20;  // most bytes of one byte run 
 
 template <class Prep, class Fin>
 int run_record_jobs(Context* c, uint8_t type, uint64_t n, uint32_t max_len, uint32_t start, hipStream_t s,
-                    Prep prep, Fin fin, const char* what, bool runs_ok = false) {
+                    Prep prep, Fin fin, const char* what, bool runs_ok = false, size_t tail_bytes = 0,
+                    void** tail = nullptr, bool reserve_runs = false) {
   const bool use_runs = runs_ok && max_len >= kRecordRunsMinLen && n * (uint64_t)max_len >= kRecordRunsBytes;
   const uint32_t nw = (uint32_t)c->cus * kWaves;
   const uint32_t rblocks = (uint32_t)std::min<uint64_t>(kRunBlocksMax, std::max<uint64_t>(1, n / 256));
   const size_t head = (16 + n * (8 + 8 + 4) + 63) / 64 * 64;
-  const size_t bytes = head + (use_runs ? (rblocks + 2 * (nw + 1)) * 8 + (nw + 1) * 4 : 0) + 64;
+  // reserve_runs: the byte-run tables are part of the size whatever max_len is, so that the pair's
+  // buffer depends on n alone.  The tail: the caller's, for its fin (own is a multiple of 4).
+  const size_t own = head + (use_runs || reserve_runs ? (rblocks + 2 * (nw + 1)) * 8 + (nw + 1) * 4 : 0) + 64;
+  const size_t bytes = own + tail_bytes;
   void* scratch = nullptr;
   if (int rc = call_scratch(c, s, bytes, &scratch)) return rc;
   uint8_t* base = (uint8_t*)scratch;
+  if (tail) *tail = base + (own + 15) / 16 * 16;
   uint32_t* maxl = (uint32_t*)base;
   uint64_t* addr = (uint64_t*)(base + 16);
   uint64_t* len = addr + n;
@@ -1329,6 +1336,73 @@ int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io* d_ios, u
         return launch_client_read_prep(d_ios, n_ios, type, max_len, addr, len, maxl, s);
       },
       merge, "client read");
+}
+
+// run_record_jobs' carve {maxl[4], addr[n], len[n], v[n]}, the byte-run tables a large prepare
+// adds (their size depends on the device: bounded here by kRunBlocksMax and 4096 waves), and
+// complete's tail.
+static size_t forward_call_bytes(uint64_t n) {
+  const size_t head = (16 + (size_t)n * (8 + 8 + 4) + 63) / 64 * 64 + 64;
+  constexpr size_t nw = 1024 * kWaves;  // (a device of 1024 CUs)
+  constexpr size_t runs = (kRunBlocksMax + 2 * (nw + 1)) * 8 + (nw + 1) * 4;
+  return head + runs + forward_scratch_bytes(n) + 16;
+}
+
+size_t hf3fs_crc_forward_scratch_bytes(uint64_t n) {
+  if (n > kForwardMaxJobs) return 0;
+  return roomy_words((forward_call_bytes(n) + 3) / 4) * 4;
+}
+
+static int forward_args(uint8_t type, const hf3fs_crc_forward_job* d_jobs, uint64_t n, const uint32_t* d_info) {
+  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (!d_jobs && n) return fail(HF3FS_CRC_INVALID_ARG, "null jobs");
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if (n > kForwardMaxJobs) return fail(HF3FS_CRC_INVALID_ARG, "too many jobs (%llu)", (unsigned long long)n);
+  return HF3FS_CRC_OK;
+}
+
+int hf3fs_crc_forward_prepare(uint8_t type, hf3fs_crc_forward_job* d_jobs, uint64_t n, uint32_t max_len,
+                              uint32_t max_inline_bytes, uint32_t* d_info, void* stream) {
+  if (int rc = forward_args(type, d_jobs, n, d_info)) return rc;
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_FORWARD_INFO_WORDS, s));  // the finish adds into it
+  if (n == 0) return HF3FS_CRC_OK;
+  // Whole stored chunks, like a scrub batch: large batches hash as byte runs (runs_ok).  The tail
+  // is complete's and the run tables are reserved in both calls, so that either call takes the same
+  // bytes for n jobs whatever max_len is: the pair's buffer never grows between the two.
+  return run_record_jobs(
+      c, type, n, max_len, ~0u, s,
+      [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
+        return launch_forward_prep(d_jobs, n, type, max_len, false, addr, len, maxl, s);
+      },
+      [&](const uint32_t* v) {
+        return launch_forward_prepare_finish(d_jobs, n, type, max_len, max_inline_bytes, v, d_info, s);
+      },
+      "forward prepare", true, forward_scratch_bytes(n) + 16, nullptr, true);
+}
+
+int hf3fs_crc_forward_complete(uint8_t type, hf3fs_crc_forward_job* d_jobs, uint64_t n, uint32_t max_len,
+                               uint32_t* d_commit_idx, uint32_t* d_info, void* stream) {
+  if (int rc = forward_args(type, d_jobs, n, d_info)) return rc;
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_FORWARD_INFO_WORDS, s));  // the finish adds into it
+  if (n == 0) return HF3FS_CRC_OK;
+  void* tail = nullptr;
+  return run_record_jobs(
+      c, type, n, max_len, ~0u, s,
+      [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
+        return launch_forward_prep(d_jobs, n, type, max_len, true, addr, len, maxl, s);
+      },
+      [&](const uint32_t* v) {
+        ForwardScratch fs;
+        forward_scratch_carve(tail, n, &fs);
+        return launch_forward_complete_finish(d_jobs, n, type, max_len, v, d_commit_idx, d_info, fs, s);
+      },
+      "forward complete", false, forward_scratch_bytes(n) + 16, &tail, true);
 }
 
 int hf3fs_crc_scrub_batch(uint8_t type, hf3fs_crc_scrub_io* d_ios, uint64_t n, uint32_t max_len,

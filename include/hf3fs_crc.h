@@ -36,6 +36,9 @@ enum { HF3FS_UPDATE_WRITE = 1, HF3FS_UPDATE_TRUNCATE = 4, HF3FS_UPDATE_EXTEND = 
 /* UpdateType::COMMIT (Common.h:57): a commit job of hf3fs_crc_update_versioned and
  * hf3fs_crc_update_engine, valid in those calls only */
 enum { HF3FS_UPDATE_COMMIT = 16 };
+/* UpdateType::REMOVE (Common.h:51-54): a job of hf3fs_crc_forward_prepare / _complete only; the
+ * update entry points keep answering kInvalidArg for it */
+enum { HF3FS_UPDATE_REMOVE = 2 };
 
 /* Status codes: the reference's numeric codes (src/common/utils/StatusCodeDetails.h). */
 enum {
@@ -51,6 +54,7 @@ enum {
   HF3FS_CRC_CHUNK_ADVANCE_UPDATE = 4012,      /* StorageCode::kChunkAdvanceUpdate (:162) */
   HF3FS_CRC_CHUNK_SIZE_MISMATCH = 4015,       /* StorageCode::kChunkSizeMismatch (:165) */
   HF3FS_CRC_CHUNK_STALE_COMMIT = 4023,        /* StorageCode::kChunkStaleCommit (:172) */
+  HF3FS_CRC_NO_SUCCESSOR_TARGET = 4033,       /* StorageCode::kNoSuccessorTarget (:177) */
   HF3FS_CRC_CHECKSUM_MISMATCH = 4080,         /* StorageCode::kChecksumMismatch (:186) */
   HF3FS_CRC_CHAIN_VERSION_MISMATCH = 4081,    /* StorageCode::kChainVersionMismatch (:187) */
   HF3FS_CRC_CHUNK_VERSION_MISMATCH = 4082,    /* StorageCode::kChunkVersionMismatch (:188) */
@@ -778,6 +782,191 @@ int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io *d_ios, u
 size_t hf3fs_crc_client_read_scratch_bytes(uint64_t n_ios, uint64_t n_parents);
 
 /* ------------------------------------------------------------------------ */
+/* chain forwarding: the hop between a target's local update and its commit   */
+/* ------------------------------------------------------------------------ */
+/* One update on a head or middle target between its local update and its commit:
+ * StorageOperator::handleUpdate (src/storage/service/StorageOperator.cc:401-485) around
+ * ReliableForwarding::forward / doForward (src/storage/service/ReliableForwarding.cc:113-134,
+ * 145-278).  The host fills the inputs from the request, the local IOResult and the target,
+ * hf3fs_crc_forward_prepare decides and builds the outgoing request, the host sends it and writes
+ * the successor's answer into the response fields, hf3fs_crc_forward_complete decides the commit.
+ * Checksums are raw, as everywhere at this ABI.  No call writes one of its own inputs. */
+typedef struct hf3fs_crc_forward_job {
+  /* request (UpdateReq.payload / .options / .featureFlags) */
+  uint64_t payload;              /*   0 device address of rdmabuf (`length` bytes; 0 for truncate / extend / remove) */
+  uint64_t chunk;                /*   8 device address of the chunk bytes [0, chunk_len): the syncing read */
+  uint32_t offset;               /*  16 UpdateIO.offset */
+  uint32_t length;               /*  20 UpdateIO.length */
+  uint32_t chunk_size;           /*  24 UpdateIO.chunkSize */
+  uint32_t req_update_ver;       /*  28 UpdateIO.updateVer as the request carries it (0: unset) */
+  uint32_t req_checksum;         /*  32 UpdateIO.checksum.value */
+  uint8_t update_type;           /*  36 HF3FS_UPDATE_{WRITE,REMOVE,TRUNCATE,EXTEND} */
+  uint8_t req_checksum_type;     /*  37 UpdateIO.checksum.type */
+  uint8_t req_flags;             /*  38 HF3FS_FORWARD_REQ_* */
+  uint8_t upd_checksum_type;     /*  39 updateResult.checksum.type */
+  /* local update result (doUpdate's IOResult) */
+  int32_t upd_status;            /*  40 0, or lengthInfo.error().code() */
+  uint32_t upd_length;           /*  44 *lengthInfo */
+  uint32_t upd_update_ver;       /*  48 */
+  uint32_t upd_commit_ver;       /*  52 */
+  uint32_t upd_checksum;         /*  56 updateResult.checksum.value */
+  /* target */
+  uint32_t chain_ver;            /*  60 target->vChainId.chainVer */
+  uint8_t has_successor;         /*  64 target->successor.has_value() */
+  uint8_t successor_syncing;     /*  65 successor's publicState == SYNCING */
+  uint8_t engine_job;            /*  66 chunkEngineJob.chunk() != nullptr */
+  uint8_t chunk_checksum_type;   /*  67 state_.chunkChecksum.type */
+  /* chunk: what the syncing read (ReliableForwarding.cc:160-190) or queryChunk (:216) finds */
+  uint32_t chunk_len;            /*  68 state_.chunkLen */
+  uint32_t chunk_checksum;       /*  72 state_.chunkChecksum.value */
+  uint32_t chunk_update_ver;     /*  76 readResult.updateVer / chunkResult->updateVer */
+  uint32_t chunk_commit_chain_ver; /* 80 batch.front().result().commitChainVer */
+  int32_t chunk_status_in;       /*  84 0, or the code the read / queryChunk failed with */
+  /* outputs of prepare */
+  uint64_t out_data;             /*  88 updateReq.payload.rdmabuf: `payload`, or `chunk` after a syncing read */
+  int32_t status;                /*  96 0 for a job that goes on; what a RETURN job answers */
+  uint32_t res_length;           /* 100 updateResult after rung A (zeros after 4082 and a bad record) */
+  uint32_t res_update_ver;       /* 104 */
+  uint32_t res_commit_ver;       /* 108 */
+  uint32_t out_offset;           /* 112 the outgoing request: zeros unless action == SEND */
+  uint32_t out_length;           /* 116 */
+  uint32_t out_checksum;         /* 120 */
+  uint32_t out_update_ver;       /* 124 */
+  uint32_t out_commit_chain_ver; /* 128 updateReq.options.commitChainVer, valid with HF3FS_FORWARD_OUT_COMMIT_CHAIN_VER */
+  uint32_t computed;             /* 132 the chunk's re-hashed value where the syncing read computed one, else 0 */
+  uint8_t action;                /* 136 HF3FS_FORWARD_{RETURN,SEND,NO_SUCCESSOR} */
+  uint8_t is_syncing;            /* 137 commitIO.isSyncing (:152) */
+  uint8_t out_update_type;       /* 138 */
+  uint8_t out_checksum_type;     /* 139 */
+  uint8_t out_flags;             /* 140 HF3FS_FORWARD_OUT_* */
+  /* the successor's response: written by the host for SEND jobs, preset by prepare for the others */
+  uint8_t fwd_checksum_type;     /* 141 */
+  uint8_t reserved0[2];          /* 142 */
+  int32_t fwd_status;            /* 144 0, or result.lengthInfo.error().code() (also a transport error's code) */
+  uint32_t fwd_length;           /* 148 */
+  uint32_t fwd_checksum;         /* 152 */
+  uint32_t fwd_commit_ver;       /* 156 */
+  uint32_t fwd_commit_chain_ver; /* 160 */
+  /* outputs of complete (prepare presets commit_ver and commit_chain_ver, see below) */
+  int32_t final_status;          /* 164 0 for COMMIT; what a RETURN job answers */
+  uint32_t commit_ver;           /* 168 commitIO.commitVer */
+  uint32_t commit_chain_ver;     /* 172 commitIO.commitChainVer */
+  uint32_t fwd_update_ver;       /* 176 forwardResult.updateVer as :251 sets it (is_syncing and forward ok), else 0:
+                                        the response's own updateVer stands */
+  uint32_t buffer_computed;      /* 180 the outgoing buffer's re-hashed value where complete computed one, else 0 */
+  uint8_t final_action;          /* 184 HF3FS_FORWARD_COMMIT or HF3FS_FORWARD_RETURN */
+  uint8_t buffer_corrupted;      /* 185 1: the re-hash after a 4080 answer differs from out_checksum (:268) */
+  uint8_t reserved1[6];          /* 186 */
+} hf3fs_crc_forward_job;         /* 192 bytes */
+
+enum { HF3FS_FORWARD_REQ_SYNCING = 1,  /* req.options.isSyncing */
+       HF3FS_FORWARD_REQ_INLINE = 2 }; /* FeatureFlags::SEND_DATA_INLINE set in req.featureFlags */
+enum { HF3FS_FORWARD_OUT_SYNCING = 1,  /* updateReq.options.isSyncing */
+       HF3FS_FORWARD_OUT_INLINE = 2,   /* SEND_DATA_INLINE in updateReq.featureFlags */
+       HF3FS_FORWARD_OUT_COMMIT_CHAIN_VER = 4 }; /* doForward set options.commitChainVer (:155,201); clear: the
+                                                    request's own value goes out */
+enum { HF3FS_FORWARD_RETURN = 1,       /* handleUpdate co_returns: `status` / `final_status` and the res_ fields */
+       HF3FS_FORWARD_SEND = 2,         /* messenger.update(out_...) to the successor, then complete */
+       HF3FS_FORWARD_NO_SUCCESSOR = 3, /* :113-117: nothing to send, complete commits */
+       HF3FS_FORWARD_COMMIT = 4 };     /* doCommit with commit_ver / commit_chain_ver / is_syncing */
+enum {                                 /* words of hf3fs_crc_forward_prepare's d_info */
+  HF3FS_FORWARD_INFO_SENT = 0,
+  HF3FS_FORWARD_INFO_RETURNED = 1,
+  HF3FS_FORWARD_INFO_NO_SUCCESSOR = 2,
+  HF3FS_FORWARD_INFO_SYNC_HASHED = 3,     /* syncing reads whose chunk bytes were hashed */
+  HF3FS_FORWARD_INFO_SYNC_MISMATCHED = 4, /* syncing reads answered 4080 (NONE-typed ones included) */
+  HF3FS_FORWARD_INFO_BAD_RECORDS = 5,     /* status 3 */
+  HF3FS_FORWARD_INFO_WORDS = 8            /* both calls; words without a name are written as 0 */
+};
+enum {                                 /* words of hf3fs_crc_forward_complete's d_info */
+  HF3FS_FORWARD_DONE_COMMITS = 0,      /* entries of d_commit_idx */
+  HF3FS_FORWARD_DONE_RETURNED = 1,     /* final_action RETURN, prepare's RETURN jobs included */
+  HF3FS_FORWARD_DONE_7015 = 2,
+  HF3FS_FORWARD_DONE_4081 = 3,
+  HF3FS_FORWARD_DONE_4082 = 4,         /* rung D's only; prepare's are `status` already */
+  HF3FS_FORWARD_DONE_REHASHED = 5,     /* outgoing buffers hashed after a 4080 answer */
+  HF3FS_FORWARD_DONE_CORRUPTED = 6,    /* buffer_corrupted set */
+  HF3FS_FORWARD_DONE_UNHASHABLE = 7    /* 4080 answers whose buffer cannot be hashed (see below): not compared */
+};
+
+/* hf3fs_crc_forward_prepare, per job, in this order.
+ *
+ * A record whose update_type is none of WRITE / REMOVE / TRUNCATE / EXTEND is RETURN 3.
+ *
+ * A. The local result (StorageOperator.cc:401-434).  upd_status 0: a req_update_ver of 0 becomes
+ * upd_update_ver (:404-405; "the request's version" below is that value, the input field is not
+ * written), any other that differs is RETURN 4082 (:406-409).  4007 and 4012: RETURN the local
+ * result as it is (:411-414, 427-430).  4008: RETURN status 0 with res_length = length and
+ * res_update_ver = res_commit_ver = the request's version (:415-421).  4006: go on with
+ * res_length = length, res_update_ver = the request's version (:422-426).  Any other code: RETURN
+ * it (:431-434).  A job that goes on has commit_ver = res_update_ver (:441).
+ *
+ * B. forward / doForward (ReliableForwarding.cc:113-222).  No successor: action NO_SUCCESSOR,
+ * commit_chain_ver = chain_ver (:115), the response fields preset to fwd_status 4033 and zeros.
+ * Otherwise is_syncing = successor_syncing (:152), and the syncing read is taken when the type is
+ * WRITE / TRUNCATE / EXTEND, is_syncing, and REQ_SYNCING or length != chunk_size (:158-159).
+ *   With it: a non-zero chunk_status_in is RETURNed (:190).  A chunk type that is neither NONE nor
+ *   `type`, chunk_len > max_len, or a null `chunk` with chunk_len > 0 is RETURN 3 and nothing is
+ *   hashed.  Else the bytes [0, chunk_len) are hashed in chunk_checksum_type and compared with
+ *   chunk_checksum (AioReadJob::setResult, src/storage/aio/BatchReadJob.cc:43-54): a NONE chunk
+ *   computes {NONE, 0} without a byte read and mismatches exactly when chunk_checksum != 0; a
+ *   mismatch is RETURN 4080.  On success the outgoing request is a WRITE of [0, chunk_len) from
+ *   `chunk` with the stored chunk checksum, out_update_ver = chunk_update_ver, SYNCING set, INLINE
+ *   set iff chunk_len <= max_inline_bytes (:193-212), out_commit_chain_ver =
+ *   chunk_commit_chain_ver with REQ_SYNCING, else chain_ver (:155,200-202).  The checksum
+ *   setResult leaves in result_ at BatchReadJob.cc:28-35 is never read by doForward: it is not
+ *   computed here.  aioFinishRead's version check (:38) stays with the host: its failure is a
+ *   chunk_status_in.
+ *   Without it: the outgoing request is the request with the request's version; with is_syncing,
+ *   not REMOVE and not engine_job a non-zero chunk_status_in is RETURNed and out_update_ver =
+ *   chunk_update_ver (:215-222); with is_syncing SYNCING is set and out_commit_chain_ver =
+ *   chain_ver (:153-156).
+ * RETURN jobs get zeroed out_ and response fields and commit_ver = commit_chain_ver = 0.
+ *
+ * hf3fs_crc_forward_complete, per job.  A job whose action is not SEND or NO_SUCCESSOR keeps its
+ * status: final_action RETURN, final_status = status.  For the others:
+ *
+ * C. The response (ReliableForwarding.cc:233-278, 120-134).  fwd_status 0: chain_ver <
+ * fwd_commit_chain_ver turns the forward result into 4081 (:238-245); otherwise commit_ver =
+ * fwd_commit_ver, commit_chain_ver = fwd_commit_chain_ver (:121-123) and, with is_syncing,
+ * fwd_update_ver = the request's version (:251).  forward's own check (:125) is restated after
+ * it and can never fire: doForward answered 4081 for the same condition already.  fwd_status
+ * 4080: the outgoing buffer [out_data, out_length) is hashed in out_checksum_type and compared
+ * with out_checksum (:263-268); a difference sets buffer_corrupted, and raising the signal
+ * (:269-274) is the host's.  A NONE type computes {NONE, 0}; a type that is neither NONE nor
+ * `type`, out_length > max_len or a null out_data with out_length > 0 is counted UNHASHABLE and not
+ * compared.  The forward result stays 4080.
+ *
+ * D. handleUpdate after the forward (StorageOperator.cc:446-485).  commit_ver != res_update_ver:
+ * RETURN 4082 (:446-453).  Forward ok: a REMOVE with fwd_checksum_type or upd_checksum_type NONE,
+ * or with is_syncing, passes (:465-474); otherwise {type, value} inequality of fwd_checksum and
+ * upd_checksum is RETURN 7015 (:475-482).  A forward error other than 4033 is RETURNed as it is
+ * (:483-485).  Everything else is COMMIT with final_status 0.  Complete reads no field it writes,
+ * so a job the host resent (forwardWithRetry's loop and its waiting are the host's) is completed
+ * again by another call.
+ *
+ * d_commit_idx (n words, may be NULL) receives the COMMIT jobs' indices in ascending order, their
+ * count goes to d_info[HF3FS_FORWARD_DONE_COMMITS].
+ *
+ * Both calls: asynchronous on `stream`, nothing synchronised or read back; capturable, also as a
+ * process's first library call, and a replayed graph works from what the records hold at replay
+ * time.  d_info (HF3FS_FORWARD_INFO_WORDS words) is set, not accumulated.  max_len >= every length
+ * that is hashed.  HF3FS_CRC_INVALID_ARG before a device is touched: a type other than CRC32C /
+ * CRC32, null d_jobs with n > 0, null d_info, n above 2^30.  n == 0 only zeroes d_info.  Only the
+ * existing range kernels load data bytes, and only of the jobs that hash; no store goes to a
+ * caller data buffer. */
+int hf3fs_crc_forward_prepare(uint8_t type, hf3fs_crc_forward_job *d_jobs, uint64_t n, uint32_t max_len,
+                              uint32_t max_inline_bytes, uint32_t *d_info, void *stream);
+int hf3fs_crc_forward_complete(uint8_t type, hf3fs_crc_forward_job *d_jobs, uint64_t n, uint32_t max_len,
+                               uint32_t *d_commit_idx, uint32_t *d_info, void *stream);
+/* An upper bound of the library-owned scratch either call takes for n jobs on any device.  Both
+ * calls take the same bytes for n jobs, whatever max_len is (prepare takes complete's share and
+ * both reserve the tables of the byte-run schedule large prepares hash with), so the pair rule of
+ * hf3fs_crc_update_scratch_bytes holds in n alone: after one call of either kind at the largest n
+ * nothing grows.  Monotone in n, 0 for n above 2^30. */
+size_t hf3fs_crc_forward_scratch_bytes(uint64_t n);
+
+/* ------------------------------------------------------------------------ */
 /* file MD5: admin `checksum --md5`                                           */
 /* ------------------------------------------------------------------------ */
 /* One run of bytes of a file, in file order. data == 0: `length` zero bytes (a hole). */
@@ -1131,5 +1320,22 @@ int hf3fs_crc_fill_synth(void *d_dst, uint64_t stride, uint64_t chunk_len, uint6
 
 #ifdef __cplusplus
 }
+/* hf3fs_crc_forward_job's layout is part of the ABI (3fs_amd/_lib.py mirrors it). */
+static_assert(sizeof(hf3fs_crc_forward_job) == 192 && sizeof(hf3fs_crc_forward_job) % 8 == 0, "forward job size");
+static_assert(offsetof(hf3fs_crc_forward_job, update_type) == 36 && offsetof(hf3fs_crc_forward_job, upd_status) == 40 &&
+                  offsetof(hf3fs_crc_forward_job, chain_ver) == 60 && offsetof(hf3fs_crc_forward_job, chunk_len) == 68 &&
+                  offsetof(hf3fs_crc_forward_job, chunk_status_in) == 84,
+              "forward job inputs");
+static_assert(offsetof(hf3fs_crc_forward_job, out_data) == 88 && offsetof(hf3fs_crc_forward_job, status) == 96 &&
+                  offsetof(hf3fs_crc_forward_job, computed) == 132 && offsetof(hf3fs_crc_forward_job, action) == 136 &&
+                  offsetof(hf3fs_crc_forward_job, out_flags) == 140,
+              "forward job prepare outputs");
+static_assert(offsetof(hf3fs_crc_forward_job, fwd_checksum_type) == 141 &&
+                  offsetof(hf3fs_crc_forward_job, fwd_status) == 144 &&
+                  offsetof(hf3fs_crc_forward_job, fwd_commit_chain_ver) == 160 &&
+                  offsetof(hf3fs_crc_forward_job, final_status) == 164 &&
+                  offsetof(hf3fs_crc_forward_job, final_action) == 184 &&
+                  offsetof(hf3fs_crc_forward_job, buffer_corrupted) == 185,
+              "forward job response and complete outputs");
 #endif
 #endif /* HF3FS_CRC_H */
