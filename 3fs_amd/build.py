@@ -85,7 +85,8 @@ CPP_TEST_BIN = os.path.join(CPP_DIR, "test_checksuminfo")
 CPP_BENCH_COALESCER = os.path.join(CPP_DIR, "bench_coalescer")
 CPP_TEST_STAGING = os.path.join(CPP_DIR, "test_staging")
 CPP_BENCH_READ = os.path.join(CPP_DIR, "bench_read_batch")
-CPP_PROGRAMS = [CPP_TEST_BIN, CPP_BENCH_COALESCER, CPP_TEST_STAGING, CPP_BENCH_READ]
+CPP_CHECK_LAYOUT = os.path.join(CPP_DIR, "check_scratch_layout")  # needs no GPU (tests/test_scratch_layout.py)
+CPP_PROGRAMS = [CPP_TEST_BIN, CPP_BENCH_COALESCER, CPP_TEST_STAGING, CPP_BENCH_READ, CPP_CHECK_LAYOUT]
 HIP_PROGRAMS = {CPP_TEST_STAGING}  # carry a probe kernel of their own: compiled by hipcc
 
 
@@ -96,7 +97,9 @@ def build_cpp_tests(force=False, verbose=False):
     oracle_c = os.path.join(REPO, "oracle", "crc_oracle.c")
     headers = [os.path.join(REPO, "include", "hf3fs", "storage", "ChecksumInfo.h"),
                os.path.join(REPO, "include", "hf3fs_crc.h")]
-    stale = [b for b in CPP_PROGRAMS if force or _stale(b, [b + ".cpp", oracle_c, lib] + headers)]
+    csrc_headers = [os.path.join(CSRC, h) for h in HEADERS]  # the layout check includes the carves' headers
+    stale = [b for b in CPP_PROGRAMS
+             if force or _stale(b, [b + ".cpp", oracle_c, lib] + headers + (csrc_headers if b == CPP_CHECK_LAYOUT else []))]
     if not stale:
         return CPP_TEST_BIN
     obj = os.path.join(CPP_DIR, "_oracle.o")

@@ -42,7 +42,7 @@ SENT32 = 0x5E5E5E5E        # every output word before a call or a replay
 SENT8 = 0x5E
 KW = 16                    # kWaves: waves per workgroup (crc_kernels.h:27)
 BLOCK = 1024               # kBlockBytes (crc_kernels.h:29)
-PIPE_MAX = 16 << 10        # kPipeMaxLen (hf3fs_crc_api.hip:331)
+PIPE_MAX = 16 << 10        # kPipeMaxLen (hf3fs_crc_api.hip)
 BYTE_BUDGET = 32 << 20     # device bytes of one case
 
 READ_DT = np.dtype([("data", "<u8"), ("offset", "<u4"), ("length", "<u4"), ("chunk_len", "<u4"),
@@ -1018,7 +1018,7 @@ SCHEDULES = ("direct_static", "direct_pipe", "direct_ticketed", "segmented_ticke
 
 
 def _make_plan(cus, n, max_len, sw, seg_hint=0):
-    """make_plan (hf3fs_crc_api.hip:336-369) -> (seg_bytes, segs, grid, pipe_max)."""
+    """make_plan (hf3fs_crc_api.hip) -> (seg_bytes, segs, grid, pipe_max)."""
     waves = cus * KW
     max_seg = max(BLOCK, -(-max_len // BLOCK) * BLOCK)
     seg, total = max_seg, n * max_len
@@ -1053,17 +1053,17 @@ def _schedule(shape, cus, switches):
     sw = dict(DEFAULTS, **{k: str(v) for k, v in (switches or {}).items()})
     entry, mem = shape["entry"], set()
     if shape.get("verify_scratch"):
-        mem.add("verify")                                           # verify_begin :738
+        mem.add("verify")                                           # verify_begin
     if entry == "scalar":
         return None, mem
-    if entry == "file_digest":                                      # file_digest_batch_ex :1082-1091
+    if entry == "file_digest":                                      # hf3fs_crc_file_digest_batch_ex
         splits = min(64, max(1, -(-shape["max_blocks"] // 2048)))   # digest_kernels.hip:335-339
         if splits > 1 or not shape["fill_zero"]:                    # digest_kernels.hip:330-333
             mem.add("call")
         return None, mem
     n, max_len = shape["n"], shape["max_len"]
     waves = cus * KW
-    if entry in ("create_strided", "verify_strided"):               # create_strided :684-720
+    if entry in ("create_strided", "verify_strided"):               # hf3fs_crc_create_strided
         whole = n % waves == 0 or n >= 8 * waves
         seg, segs, grid, pipe_max = _make_plan(cus, n, max_len, sw, max(max_len, 1) if whole else 0)
         per_wave = n * max_len // waves
@@ -1073,30 +1073,30 @@ def _schedule(shape, cus, switches):
         if big and ((not whole and segs > 1) or window):
             mem.add("call")
             return ("byte_runs" if rep == 1 else "byte_runs_rep"), mem
-        if n * segs > grid * KW and sw["static"] == "0":            # launch_prepare :381 (the counter is then dropped, :718)
+        if n * segs > grid * KW and sw["static"] == "0":            # launch_prepare (create_strided then drops the counter)
             mem.add("counter")
         return _kernel(n, segs, grid, segs == 1, False, False, seg, pipe_max), mem
     if entry in ("create_batch", "verify_batch", "verify_blocks"):
-        if entry != "verify_blocks" and sw["list_runs"] != "0":     # create_batch :654-664
+        if entry != "verify_blocks" and sw["list_runs"] != "0":     # hf3fs_crc_create_batch
             mem.add("call")
             return ("byte_runs" if int(sw["prehash_rep"]) <= 1 else "byte_runs_rep"), mem
         seg, segs, grid, pipe_max = _make_plan(cus, n, max_len, sw)
-        queue = n * segs > grid * KW and sw["static"] == "0"        # launch_prepare :381, tickets_allowed :372
+        queue = n * segs > grid * KW and sw["static"] == "0"        # launch_prepare, tickets_allowed
         if queue:
             mem.add("counter")
-        bal = sw["balance"] != "0" and segs == 1 and max_len > pipe_max and n > 16 * grid * KW  # plan_balance :397
+        bal = sw["balance"] != "0" and segs == 1 and max_len > pipe_max and n > 16 * grid * KW  # plan_balance
         if bal:
             mem.add("balance")
-            queue = False                                           # plan_balance :408: the plan carries no queue
+            queue = False                                           # plan_balance: the plan carries no queue
             if sw["range_stream"] != "0":                           # launch_poly, crc_kernels.hip:523
                 return "range_stream", mem
         return _kernel(n, segs, grid, segs == 1, queue, bal, seg, pipe_max), mem
-    mem.add("call")                                                 # record jobs :481, frames :1040
-    if entry == "frames":                                           # frame_verify_batch :1029, k_frame_map frame_kernels.hip:123
+    mem.add("call")                                                 # run_record_jobs, hf3fs_crc_frame_verify_batch
+    if entry == "frames":                                           # hf3fs_crc_frame_verify_batch, k_frame_map frame_kernels.hip:123
         try_stream = n >= 256 if sw["frame_stream"] == "auto" else sw["frame_stream"] != "0"
         if try_stream and shape["sorted_ok"] and shape["gap"] <= shape["pay"]:
             return "frame_stream", mem
-    elif shape.get("runs_ok") and max_len >= (64 << 10) and n * max_len >= (1 << 30):  # run_record_jobs :475
+    elif shape.get("runs_ok") and max_len >= (64 << 10) and n * max_len >= (1 << 30):  # run_record_jobs
         return "byte_runs", mem
     seg, segs, grid, pipe_max = _make_plan(cus, n, max_len, sw)
     m = shape["dev_max"]
@@ -1104,15 +1104,15 @@ def _schedule(shape, cus, switches):
         return "all_empty", mem                                     # crc_kernels.hip:395
     direct_t = segs == 1 and sw["record_direct"] != "0"             # launch_poly, crc_kernels.hip:533-534
     dsegs = -(-m // seg) if m > seg else 1                          # crc_kernels.hip:400
-    queue = sw["static"] == "0"                                     # a device-side bound always asks for tickets :381/:448
-    return _kernel(n, dsegs, cus, direct_t or dsegs == 1, queue, False, m, pipe_max), mem  # grid = cus :434
+    queue = sw["static"] == "0"                                     # a device-side bound always asks for tickets (launch_prepare, run_ranges_list)
+    return _kernel(n, dsegs, cus, direct_t or dsegs == 1, queue, False, m, pipe_max), mem  # grid = cus (run_ranges_list)
 
 
 def expected_schedule(shape, cus, switches=None):
     """Which schedule of the hot kernel a launch takes: a plain restatement of make_plan,
-    launch_prepare and plan_balance (hf3fs_crc_api.hip:336-410), the host branches of
-    create_batch and create_strided (:641-721), run_record_jobs (:472-507), the frame route
-    (:1027-1062, frame_kernels.hip:105-127), launch_poly (crc_kernels.hip:520-539) and
+    launch_prepare and plan_balance (hf3fs_crc_api.hip), the host branches of
+    hf3fs_crc_create_batch, hf3fs_crc_create_strided and run_record_jobs (hf3fs_crc_api.hip), the
+    frame route (hf3fs_crc_frame_verify_batch, frame_kernels.hip:105-127), launch_poly (crc_kernels.hip:520-539) and
     k_crc_ranges' own choices (crc_kernels.hip:391-434: tickets dropped for ntasks <= W or
     > 16 W, direct_pipe for len_bound <= pipe_max, direct || segs == 1).  Returns one of SCHEDULES;
     beside them "frame_stream" for a frame batch the stream path takes, "all_empty" for a record
@@ -1126,7 +1126,7 @@ def expected_schedule(shape, cus, switches=None):
 
 
 def library_memory(shape, cus, switches=None):
-    """The kinds of library memory the launch asks call_memory for (hf3fs_crc_api.hip:300-316): a
+    """The kinds of library memory the launch asks call_memory for (hf3fs_crc_api.hip): a
     subset of {"verify", "call", "balance", "counter"}.  A captured call owns one graph buffer per
     kind (small ones share a slab).  Same caveat as expected_schedule."""
     return _schedule(shape, cus, switches)[1]
@@ -1148,24 +1148,24 @@ _RANGES = _LIST + ["create_strided"] + _VLIST + _VSTRIDED + _VBLOCKS + _RECORD
 
 # (name, value) pairs set together -> the cases the row applies to, and where the code reads the switch
 SWITCHES = {
-    (("nt", "0"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip:364 make_plan, crc_kernels.hip:524-538 launch_poly"),
-    (("static", "1"),): dict(cases=_LIST + _VLIST + _VBLOCKS + _RECORD, source="hf3fs_crc_api.hip:372 tickets_allowed"),
-    (("seg_kib", "1"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip:343 make_plan"),
-    (("seg_kib", "4"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip:343 make_plan"),
-    (("seg_kib", "64"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip:343 make_plan"),
+    (("nt", "0"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip make_plan, crc_kernels.hip launch_poly"),
+    (("static", "1"),): dict(cases=_LIST + _VLIST + _VBLOCKS + _RECORD, source="hf3fs_crc_api.hip tickets_allowed"),
+    (("seg_kib", "1"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip make_plan"),
+    (("seg_kib", "4"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip make_plan"),
+    (("seg_kib", "64"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip make_plan"),
     (("balance", "0"),): dict(cases=["create_list_small_many_balanced"] + _VBLOCKS,
-                              source="hf3fs_crc_api.hip:394 plan_balance"),
-    (("record_direct", "0"),): dict(cases=_RECORD, source="crc_kernels.hip:533 launch_poly"),
-    (("pipe", "0"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip:365-366 make_plan"),
-    (("pipe", "1"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip:365-366 make_plan"),
+                              source="hf3fs_crc_api.hip plan_balance"),
+    (("record_direct", "0"),): dict(cases=_RECORD, source="crc_kernels.hip launch_poly"),
+    (("pipe", "0"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip make_plan"),
+    (("pipe", "1"),): dict(cases=_RANGES, source="hf3fs_crc_api.hip make_plan"),
     (("range_stream", "1"),): dict(cases=["create_list_small_many_balanced"] + _VBLOCKS,
-                                   source="hf3fs_crc_api.hip:367 make_plan and :408 plan_balance, crc_kernels.hip:523 launch_poly"),
-    (("list_runs", "1"), ("prehash_rep", "1")): dict(cases=_LIST + _VLIST, source="hf3fs_crc_api.hip:654-655 create_batch"),
-    (("list_runs", "1"), ("prehash_rep", "8")): dict(cases=_LIST + _VLIST, source="hf3fs_crc_api.hip:654-655 create_batch"),
-    (("frame_stream", "0"), ("frame_segw", "1")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip:1028-1031 frame_verify_batch"),
-    (("frame_stream", "0"), ("frame_segw", "64")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip:1028-1031 frame_verify_batch"),
-    (("frame_stream", "1"), ("frame_segw", "1")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip:1028-1031 frame_verify_batch"),
-    (("frame_stream", "1"), ("frame_segw", "64")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip:1028-1031 frame_verify_batch"),
+                                   source="hf3fs_crc_api.hip make_plan and plan_balance, crc_kernels.hip launch_poly"),
+    (("list_runs", "1"), ("prehash_rep", "1")): dict(cases=_LIST + _VLIST, source="hf3fs_crc_api.hip hf3fs_crc_create_batch"),
+    (("list_runs", "1"), ("prehash_rep", "8")): dict(cases=_LIST + _VLIST, source="hf3fs_crc_api.hip hf3fs_crc_create_batch"),
+    (("frame_stream", "0"), ("frame_segw", "1")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip hf3fs_crc_frame_verify_batch"),
+    (("frame_stream", "0"), ("frame_segw", "64")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip hf3fs_crc_frame_verify_batch"),
+    (("frame_stream", "1"), ("frame_segw", "1")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip hf3fs_crc_frame_verify_batch"),
+    (("frame_stream", "1"), ("frame_segw", "64")): dict(cases=_FRAMES, source="hf3fs_crc_api.hip hf3fs_crc_frame_verify_batch"),
 }
 
 # Switches this file does not cover, and the tests that do.

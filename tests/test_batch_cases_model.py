@@ -55,7 +55,10 @@ def test_every_switch_is_covered_or_exempt(hf):
         assert (name in covered) != (name in bc.EXEMPT), f"switch {name}: a row of SWITCHES or a reason in EXEMPT"
     assert covered | set(bc.EXEMPT) == set(names), "a row or an exemption names a switch the library does not have"
     for row, spec in bc.SWITCHES.items():
-        assert spec["cases"] and set(spec["cases"]) <= set(bc.CASES) and re.search(r":\d+", spec["source"]), row
+        cited = re.findall(r"(\w+\.(?:hip|h|cc)) (\w+)", spec["source"])  # file and function, no line numbers
+        assert spec["cases"] and set(spec["cases"]) <= set(bc.CASES) and cited, row
+        for unit, function in cited:
+            assert function in open(os.path.join(REPO, "3fs_amd", "csrc", unit)).read(), (row, unit, function)
         assert any(v != bc.DEFAULTS[k] for k, v in row), f"{row} sets nothing"
     for k, v in bc.DEFAULTS.items():
         assert L.get_option(k) == v, f"the model's default of {k}"

@@ -30,8 +30,8 @@ torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 LINE = 16 << 10
-K_STAGE = 32 << 20      # Context::kStage, 3fs_amd/csrc/hf3fs_crc_api.hip:186
-K_MAX_PIECES = 4096     # kMaxPieces, 3fs_amd/csrc/hf3fs_crc_api.hip:1336
+K_STAGE = 32 << 20      # Context::kStage, 3fs_amd/csrc/hf3fs_crc_api.hip
+K_MAX_PIECES = 4096     # kMaxPieces, create_host_staged in 3fs_amd/csrc/hf3fs_crc_api.hip
 NT0 = (("nt", "0"),)
 
 

@@ -27,7 +27,7 @@ import test_gpu_stream_queue as stream_queue  # noqa: E402
 import test_gpu_sync_plan as sync_plan  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOMY = 256 << 10  # the granule of a pair's call buffer (hf3fs_crc_api.hip)
+ROOMY = 256 << 10  # the granule of a pair's call buffer (roomy_words, hf3fs_crc_api.hip)
 SEED = 0x5EED
 
 

@@ -146,7 +146,7 @@ def test_queued_update_rounds(hf, orc, dev, opts, row):
     L.release_stream(st)
 
 
-ROOMY = 256 << 10  # pair_buffer sizes the call buffer up to a multiple of 64 Ki words (hf3fs_crc_api.hip)
+ROOMY = 256 << 10  # pair_buffer sizes the call buffer up to a multiple of 64 Ki words (roomy_words, hf3fs_crc_api.hip)
 
 
 @pytest.mark.parametrize("mode", [0, 1])
