@@ -31,6 +31,11 @@ from ._lib import (CHUNK_NOT_FOUND, CLIENT_NOT_INITIALIZED, CLIENT_READ_INFO_NAM
                    CLIENT_READ_INFO_WORDS, CLIENT_READ_NONE, CLIENT_READ_VERIFY, ClientReadIO, ClientReadResult,
                    block_digest_dtype, client_read_batch, client_read_io_dtype, client_read_result_dtype,
                    client_read_scratch_bytes)
+from ._lib import (CLIENT_INVALID_ARG, CLIENT_WRITE_DONE_NAMES, CLIENT_WRITE_DONE_WORDS,  # noqa: F401
+                   CLIENT_WRITE_FROM_UPDATES, CLIENT_WRITE_INFO_NAMES, CLIENT_WRITE_INFO_WORDS, CLIENT_WRITE_NONE,
+                   CLIENT_WRITE_VERIFY, INVALID_FORMAT, ClientWriteFile, ClientWriteIO, client_write_complete,
+                   client_write_file_dtype, client_write_io_dtype, client_write_prepare, client_write_scratch_bytes,
+                   update_io_dtype)
 from ._lib import (FORWARD_COMMIT, FORWARD_DONE_NAMES, FORWARD_INFO_NAMES, FORWARD_INFO_WORDS,  # noqa: F401
                    FORWARD_NO_SUCCESSOR, FORWARD_OUT_COMMIT_CHAIN_VER, FORWARD_OUT_INLINE, FORWARD_OUT_SYNCING,
                    FORWARD_REQ_INLINE, FORWARD_REQ_SYNCING, FORWARD_RETURN, FORWARD_SEND, NO_SUCCESSOR_TARGET,

@@ -182,6 +182,53 @@ CLIENT_READ_INFO_NAMES = ("bad_children", "bad_parents", "hard_parents", "reserv
 CLIENT_READ_NONE = 0xFFFFFFFF  # ClientReadResult.failed_child: no child took over
 
 
+class ClientWriteIO(ctypes.Structure):
+    """hf3fs_crc_client_write_io: one WriteIO of a batchWrite (StorageClientImpl.cc:889-951, 994-1015,
+    1878-1901) and its answer (FileWrapper.cc:218-248)."""
+    _fields_ = [
+        ("data", ctypes.c_uint64),
+        ("buf_base", ctypes.c_uint64),
+        ("buf_size", ctypes.c_uint64),
+        ("offset", ctypes.c_uint32),
+        ("length", ctypes.c_uint32),
+        ("chunk_size", ctypes.c_uint32),
+        ("checksum", ctypes.c_uint32),
+        ("checksum_type", ctypes.c_uint8),
+        ("send_inline", ctypes.c_uint8),
+        ("reserved0", ctypes.c_uint8 * 2),
+        ("status", ctypes.c_int32),
+        ("status_in", ctypes.c_int32),
+        ("result_len", ctypes.c_uint32),
+        ("result_checksum", ctypes.c_uint32),
+        ("result_checksum_type", ctypes.c_uint8),
+        ("reserved1", ctypes.c_uint8 * 3),
+    ]
+
+
+class ClientWriteFile(ctypes.Structure):
+    """hf3fs_crc_client_write_file: what writeFile returns for one file."""
+    _fields_ = [
+        ("length", ctypes.c_uint64),
+        ("value", ctypes.c_uint32),
+        ("type", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 3),
+        ("status", ctypes.c_int32),
+        ("failed_io", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(ClientWriteIO) == 64 and ctypes.sizeof(ClientWriteFile) == 24
+assert ClientWriteIO.status.offset == 44 and ClientWriteIO.result_checksum_type.offset == 60
+CLIENT_INVALID_ARG, INVALID_FORMAT = 7002, 33
+CLIENT_WRITE_VERIFY, CLIENT_WRITE_FROM_UPDATES = 1, 2  # flags of client_write_prepare / _complete
+CLIENT_WRITE_INFO_WORDS = 8
+CLIENT_WRITE_INFO_NAMES = ("sent", "range", "bad_records", "poisoned", "inline", "hashed_lo", "hashed_hi", "reserved")
+CLIENT_WRITE_DONE_WORDS = 8
+CLIENT_WRITE_DONE_NAMES = ("failed", "ok", "len_lo", "len_hi", "bad_files", "mismatched_files", "reserved0",
+                           "reserved1")
+CLIENT_WRITE_NONE = 0xFFFFFFFF  # ClientWriteFile.failed_io: no IO ended the fold
+
+
 _u8c, _u32c, _i32c, _u64c = ctypes.c_uint8, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64
 
 
@@ -385,6 +432,9 @@ SIGNATURES = {
     "hf3fs_crc_read_result_batch": (_int, [_u8, _vp, _u64, _u32, _vp]),
     "hf3fs_crc_client_read_batch": (_int, [_u8, _vp, _u64, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
     "hf3fs_crc_client_read_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
+    "hf3fs_crc_client_write_prepare": (_int, [_u8, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "hf3fs_crc_client_write_complete": (_int, [_vp, _u64, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "hf3fs_crc_client_write_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
     "hf3fs_crc_forward_prepare": (_int, [_u8, _vp, _u64, _u32, _u32, _vp, _vp]),
     "hf3fs_crc_forward_complete": (_int, [_u8, _vp, _u64, _u32, _vp, _vp, _vp]),
     "hf3fs_crc_forward_scratch_bytes": (ctypes.c_size_t, [_u64]),
@@ -679,6 +729,56 @@ def client_read_batch(ctype, ios, n_ios, info, parent_off=None, n_parents=None, 
 def client_read_scratch_bytes(n_ios, n_parents):
     """Bytes of library-owned scratch one verifying client_read_batch takes (0: rejected counts)."""
     return int(load().hf3fs_crc_client_read_scratch_bytes(n_ios, n_parents))
+
+
+def _dtype_of(struct):
+    import numpy as np
+    kinds = {_u8c: "u1", _u32c: "<u4", _i32c: "<i4", _u64c: "<u8"}
+    return np.dtype([(name, kinds[t]) if t in kinds else (name, "u1", (ctypes.sizeof(t),))
+                     for name, t in struct._fields_])
+
+
+def client_write_io_dtype():
+    """numpy dtype of hf3fs_crc_client_write_io (include/hf3fs_crc.h): one 64-byte record per IO."""
+    return _dtype_of(ClientWriteIO)
+
+
+def client_write_file_dtype():
+    """numpy dtype of hf3fs_crc_client_write_file: one 24-byte record per file."""
+    return _dtype_of(ClientWriteFile)
+
+
+def update_io_dtype():
+    """numpy dtype of hf3fs_crc_update_io: the 56-byte record client_write_prepare fills the request of."""
+    return _dtype_of(UpdateIO)
+
+
+def client_write_prepare(ctype, ios, n, info, max_len, max_inline_bytes=0, verify=True, updates=None, flags=None,
+                         stream=None):
+    """hf3fs_crc_client_write_prepare: ios a device array of hf3fs_crc_client_write_io (checksum,
+    checksum_type, send_inline and status written in place), updates a device array of
+    hf3fs_crc_update_io or None, info CLIENT_WRITE_INFO_WORDS device u32.  flags overrides verify."""
+    if flags is None:
+        flags = CLIENT_WRITE_VERIFY if verify else 0
+    return check(load().hf3fs_crc_client_write_prepare(ctype, _p(ios), n, max_len, max_inline_bytes, flags,
+                                                       _p(updates), _p(info), _s(stream)))
+
+
+def client_write_complete(ios, n, info, file_off=None, n_files=0, max_ios_per_file=1, updates=None, expected=None,
+                          files=None, failed=None, failed_cap=0, flags=None, stream=None):
+    """hf3fs_crc_client_write_complete: file_off n_files + 1 device uint64, expected n_files device
+    u32 or None, files a device array of hf3fs_crc_client_write_file, failed failed_cap device u32,
+    info CLIENT_WRITE_DONE_WORDS device u32.  flags defaults to FROM_UPDATES when updates is given."""
+    if flags is None:
+        flags = CLIENT_WRITE_FROM_UPDATES if updates is not None else 0
+    return check(load().hf3fs_crc_client_write_complete(_p(ios), n, _p(file_off), n_files, max_ios_per_file, flags,
+                                                        _p(updates), _p(expected), _p(files), _p(failed), failed_cap,
+                                                        _p(info), _s(stream)))
+
+
+def client_write_scratch_bytes(n, n_files=0):
+    """Bytes of library-owned scratch either client_write call takes for n IOs (0: rejected counts)."""
+    return int(load().hf3fs_crc_client_write_scratch_bytes(n, n_files))
 
 
 def forward_job_dtype():

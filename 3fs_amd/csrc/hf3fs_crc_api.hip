@@ -24,6 +24,8 @@
 #include "capture_scratch.h"
 #include "client_read_kernels.h"
 #include "client_read_plan.h"  // kClientMaxCount
+#include "client_write_kernels.h"
+#include "client_write_plan.h"  // kClientWriteMaxCount
 #include "frame_kernels.h"
 #include "crc_kernels.h"
 #include "digest_kernels.h"
@@ -43,6 +45,30 @@ static_assert(sizeof(hf3fs_crc_update_io) == 56, "hf3fs_crc_update_io ABI layout
 static_assert(sizeof(hf3fs_crc_read_io) == 48, "hf3fs_crc_read_io ABI layout");
 static_assert(sizeof(hf3fs_crc_client_read_io) == 40 && sizeof(hf3fs_crc_client_read_result) == 24,
               "hf3fs_crc_client_read_io / _result ABI layout");
+static_assert(sizeof(hf3fs_crc_client_write_io) == 64 && offsetof(hf3fs_crc_client_write_io, data) == 0 &&
+                  offsetof(hf3fs_crc_client_write_io, buf_base) == 8 &&
+                  offsetof(hf3fs_crc_client_write_io, buf_size) == 16 &&
+                  offsetof(hf3fs_crc_client_write_io, offset) == 24 &&
+                  offsetof(hf3fs_crc_client_write_io, length) == 28 &&
+                  offsetof(hf3fs_crc_client_write_io, chunk_size) == 32 &&
+                  offsetof(hf3fs_crc_client_write_io, checksum) == 36 &&
+                  offsetof(hf3fs_crc_client_write_io, checksum_type) == 40 &&
+                  offsetof(hf3fs_crc_client_write_io, send_inline) == 41 &&
+                  offsetof(hf3fs_crc_client_write_io, reserved0) == 42 &&
+                  offsetof(hf3fs_crc_client_write_io, status) == 44 &&
+                  offsetof(hf3fs_crc_client_write_io, status_in) == 48 &&
+                  offsetof(hf3fs_crc_client_write_io, result_len) == 52 &&
+                  offsetof(hf3fs_crc_client_write_io, result_checksum) == 56 &&
+                  offsetof(hf3fs_crc_client_write_io, result_checksum_type) == 60 &&
+                  offsetof(hf3fs_crc_client_write_io, reserved1) == 61,
+              "hf3fs_crc_client_write_io ABI layout");
+static_assert(sizeof(hf3fs_crc_client_write_file) == 24 && offsetof(hf3fs_crc_client_write_file, length) == 0 &&
+                  offsetof(hf3fs_crc_client_write_file, value) == 8 &&
+                  offsetof(hf3fs_crc_client_write_file, type) == 12 &&
+                  offsetof(hf3fs_crc_client_write_file, reserved) == 13 &&
+                  offsetof(hf3fs_crc_client_write_file, status) == 16 &&
+                  offsetof(hf3fs_crc_client_write_file, failed_io) == 20,
+              "hf3fs_crc_client_write_file ABI layout");
 static_assert(sizeof(hf3fs_crc_block_digest) == 24, "hf3fs_crc_block_digest ABI layout");
 static_assert(sizeof(hf3fs_crc_file_digest) == 24, "hf3fs_crc_file_digest ABI layout");
 static_assert(sizeof(hf3fs_crc_scrub_io) == 32, "hf3fs_crc_scrub_io ABI layout");
@@ -1336,6 +1362,98 @@ int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io* d_ios, u
         return launch_client_read_prep(d_ios, n_ios, type, max_len, addr, len, maxl, s);
       },
       merge, "client read");
+}
+
+// Prepare takes run_record_jobs' carve {ctl[4], addr[n], len[n], v[n]} with the byte-run tables
+// reserved (their size depends on the device: bounded here by kRunBlocksMax and 4096 waves),
+// complete client_write_scratch_bytes; a caller sizes for the larger.
+static size_t client_write_call_bytes(uint64_t n) {
+  const size_t head = (16 + (size_t)n * (8 + 8 + 4) + 63) / 64 * 64 + 64;
+  constexpr size_t nw = 1024 * kWaves;  // (a device of 1024 CUs)
+  constexpr size_t runs = (kRunBlocksMax + 2 * (nw + 1)) * 8 + (nw + 1) * 4;
+  return std::max(head + runs, client_write_scratch_bytes(n) + 16);
+}
+
+size_t hf3fs_crc_client_write_scratch_bytes(uint64_t n, uint64_t n_files) {
+  if (n > kClientWriteMaxCount || n_files > kClientWriteMaxCount) return 0;
+  return roomy_words((client_write_call_bytes(n) + 3) / 4) * 4;  // (the files take no scratch)
+}
+
+int hf3fs_crc_client_write_prepare(uint8_t type, hf3fs_crc_client_write_io* d_ios, uint64_t n, uint32_t max_len,
+                                   uint32_t max_inline_bytes, uint32_t flags, hf3fs_crc_update_io* d_updates,
+                                   uint32_t* d_info, void* stream) {
+  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (flags & ~(uint32_t)HF3FS_CLIENT_WRITE_VERIFY) return fail(HF3FS_CRC_INVALID_ARG, "unknown flags %#x", flags);
+  if (!d_ios && n) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if (n > kClientWriteMaxCount) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_CLIENT_WRITE_INFO_WORDS, s));  // the finish adds into it
+  if (n == 0) return HF3FS_CRC_OK;
+  const bool verify = (flags & HF3FS_CLIENT_WRITE_VERIFY) != 0;
+  const uint32_t* poison = nullptr;  // the prep's ctl + 1
+  const auto finish = [&](const uint32_t* v) {
+    return launch_client_write_prepare_finish(d_ios, n, type, max_len, max_inline_bytes, verify, v, poison, d_updates,
+                                              d_info, s);
+  };
+  if (!verify) {  // no payload is hashed: the checks alone, behind the poison word
+    void* scratch = nullptr;
+    if (int rc = call_scratch(c, s, 16, &scratch)) return rc;
+    uint32_t* ctl = (uint32_t*)scratch;
+    poison = ctl + 1;
+    HIP_OR_FAIL(launch_zero_words(ctl, 4, s));
+    HIP_OR_FAIL(launch_client_write_prep(d_ios, n, max_len, false, nullptr, nullptr, ctl, s));
+    HIP_OR_FAIL(finish(nullptr));
+    return HF3FS_CRC_OK;
+  }
+  // Batches of chunk-sized payloads hash as byte runs, like a scrub batch (4096 x 4 MiB: 2.54 ms
+  // against 2.59 ms for create_batch).  A batch of small IOs does not: 1 Mi IOs of 4-64 KiB ran
+  // 38 % slower as byte runs than create_batch's planner over the same bytes (profiles/
+  // client_write.jsonl, record prepare_mix_runs), so the runs start at a bound of 1 MiB, the
+  // planner's segment.  The run tables are reserved whatever max_len is.
+  const bool runs_ok = max_len >= kClientWriteRunsMinLen;
+  return run_record_jobs(
+      c, type, n, max_len, ~0u, s,
+      [&](uint64_t* addr, uint64_t* len, uint32_t* ctl) {
+        poison = ctl + 1;  // (run_record_jobs zeroes the four words; the range kernels read ctl[0] only)
+        return launch_client_write_prep(d_ios, n, max_len, true, addr, len, ctl, s);
+      },
+      finish, "client write prepare", runs_ok, 0, nullptr, true);
+}
+
+int hf3fs_crc_client_write_complete(hf3fs_crc_client_write_io* d_ios, uint64_t n, const uint64_t* d_file_off,
+                                    uint64_t n_files, uint64_t max_ios_per_file, uint32_t flags,
+                                    const hf3fs_crc_update_io* d_updates, const uint32_t* d_expected,
+                                    hf3fs_crc_client_write_file* d_files, uint32_t* d_failed, uint64_t failed_cap,
+                                    uint32_t* d_info, void* stream) {
+  if (flags & ~(uint32_t)HF3FS_CLIENT_WRITE_FROM_UPDATES) return fail(HF3FS_CRC_INVALID_ARG, "unknown flags %#x", flags);
+  if (!d_ios && n) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if (n > kClientWriteMaxCount || n_files > kClientWriteMaxCount)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many IOs or files (%llu, %llu)", (unsigned long long)n,
+                (unsigned long long)n_files);
+  const bool from_updates = (flags & HF3FS_CLIENT_WRITE_FROM_UPDATES) != 0;
+  if (from_updates && !d_updates) return fail(HF3FS_CRC_INVALID_ARG, "FROM_UPDATES needs update records");
+  if (n_files && (!d_file_off || !d_files)) return fail(HF3FS_CRC_INVALID_ARG, "files need offsets and records");
+  if (failed_cap && !d_failed) return fail(HF3FS_CRC_INVALID_ARG, "null failed list");
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_CLIENT_WRITE_DONE_WORDS, s));  // the kernels add into it
+  if (n) {
+    void* scratch = nullptr;
+    if (int rc = call_scratch(c, s, client_write_scratch_bytes(n) + 16, &scratch)) return rc;
+    ClientWriteScratch cs;
+    client_write_scratch_carve((void*)(((uintptr_t)scratch + 15) & ~(uintptr_t)15), n, &cs);
+    HIP_OR_FAIL(launch_client_write_settle(d_ios, n, from_updates ? d_updates : nullptr, d_failed, failed_cap, d_info,
+                                           cs, s));
+  }
+  if (n_files)
+    HIP_OR_FAIL(launch_client_write_fold(d_ios, n, d_file_off, n_files, max_ios_per_file > kClientWriteLaneMaxIos,
+                                         d_expected, d_files, d_info, c->tables, s));
+  return HF3FS_CRC_OK;
 }
 
 // run_record_jobs' carve {maxl[4], addr[n], len[n], v[n]}, the byte-run tables a large prepare

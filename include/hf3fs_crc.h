@@ -782,6 +782,132 @@ int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io *d_ios, u
 size_t hf3fs_crc_client_read_scratch_bytes(uint64_t n_ios, uint64_t n_parents);
 
 /* ------------------------------------------------------------------------ */
+/* client batchWrite: the checks and checksums before the send, the fold after */
+/* ------------------------------------------------------------------------ */
+/* One WriteIO of StorageClientImpl::batchWrite (src/client/storage/StorageClientImpl.cc:889-951,
+ * 994-1015, 1878-1901 read the request fields; FileWrapper::writeFile,
+ * src/client/cli/admin/FileWrapper.cc:218-248, reads the answer). */
+typedef struct hf3fs_crc_client_write_io {
+  uint64_t data;              /* device address of writeIO->data */
+  uint64_t buf_base;          /* writeIO->buffer->data(); 0: buffer == nullptr */
+  uint64_t buf_size;          /* the IOBuffer's capacity */
+  uint32_t offset, length, chunk_size;
+  /* outputs of prepare */
+  uint32_t checksum;          /* writeIO->checksum.value (raw) */
+  uint8_t  checksum_type;
+  uint8_t  send_inline;       /* 1: length <= max_inline_bytes */
+  uint8_t  reserved0[2];
+  int32_t  status;            /* 0: to be sent; 7002; 3 for a bad record */
+  /* the answer: inputs of complete (written by complete only with FROM_UPDATES) */
+  int32_t  status_in;         /* 0, or result.lengthInfo.error().code(); 7003 when never sent */
+  uint32_t result_len;        /* *result.lengthInfo */
+  uint32_t result_checksum;   /* result.checksum.value (raw) */
+  uint8_t  result_checksum_type;
+  uint8_t  reserved1[3];
+} hf3fs_crc_client_write_io;  /* 64 bytes */
+
+/* What writeFile returns for one file: the fold of its IOs' answers. */
+typedef struct hf3fs_crc_client_write_file {
+  uint64_t length;            /* sum of the folded succLength; 0 when status != 0 */
+  uint32_t value;             /* the folded checksum value (raw); 0 when status != 0 */
+  uint8_t  type;              /* the folded checksum type; NONE when status != 0 */
+  uint8_t  reserved[3];
+  int32_t  status;            /* 0, or the code that ended the fold */
+  uint32_t failed_io;         /* index in d_ios of the IO that ended the fold, ~0u if none */
+} hf3fs_crc_client_write_file; /* 24 bytes */
+
+enum { HF3FS_CRC_CLIENT_INVALID_ARG = 7002 };     /* StorageClientCode::kInvalidArg (:223) */
+enum { HF3FS_CLIENT_WRITE_VERIFY = 1,             /* prepare: options.verifyChecksum() (:1880) */
+       HF3FS_CLIENT_WRITE_FROM_UPDATES = 2 };     /* complete: the answers are d_updates' outputs */
+enum {                                            /* words of hf3fs_crc_client_write_prepare's d_info */
+  HF3FS_CLIENT_WRITE_INFO_SENT = 0,               /* IOs with status 0 */
+  HF3FS_CLIENT_WRITE_INFO_RANGE = 1,              /* IOs that failed their own range check (7002, rule 2) */
+  HF3FS_CLIENT_WRITE_INFO_BAD_RECORDS = 2,        /* IOs with length > max_len (3, rule 1) */
+  HF3FS_CLIENT_WRITE_INFO_POISONED = 3,           /* 0 / 1: the buffer check failed the batch (rule 3) */
+  HF3FS_CLIENT_WRITE_INFO_INLINE = 4,             /* sent IOs with send_inline */
+  HF3FS_CLIENT_WRITE_INFO_HASHED_LO = 5,          /* bytes hashed: the lengths of the individually valid IOs */
+  HF3FS_CLIENT_WRITE_INFO_HASHED_HI = 6,          /*   with VERIFY (also those of a poisoned batch), 64 bits */
+  HF3FS_CLIENT_WRITE_INFO_WORDS = 8               /* (word 7 is written as 0) */
+};
+enum {                                            /* words of hf3fs_crc_client_write_complete's d_info */
+  HF3FS_CLIENT_WRITE_DONE_FAILED = 0,             /* IOs whose final status is not 0 (collectFailedOps, :211-236) */
+  HF3FS_CLIENT_WRITE_DONE_OK = 1,                 /* numProcessedChunks: IOs whose final status is 0 */
+  HF3FS_CLIENT_WRITE_DONE_LEN_LO = 2,             /* totalDataLen (:1958-1968): result_len over the OK IOs, */
+  HF3FS_CLIENT_WRITE_DONE_LEN_HI = 3,             /*   64 bits */
+  HF3FS_CLIENT_WRITE_DONE_BAD_FILES = 4,          /* files whose status is not 0 */
+  HF3FS_CLIENT_WRITE_DONE_MISMATCHED_FILES = 5,   /* files with 7015 (d_expected) */
+  HF3FS_CLIENT_WRITE_DONE_WORDS = 8               /* (words 6 and 7 are written as 0) */
+};
+
+/* What batchWrite does with n WriteIOs before it sends them, on the device.  Per IO, in this order:
+ *
+ * 1. A bad record: length > max_len gives status 3.  The IO is not hashed, is not sent and takes no
+ *    part in rule 3.
+ * 2. Its own range (validateWriteDataRange, :994-1015): chunk_size == 0 or
+ *    (uint32_t)(offset + length) > chunk_size gives 7002 for this IO alone; the sum is the
+ *    reference's uint32_t arithmetic and wraps.  The IO takes no part in rule 3.
+ * 3. The buffer check (validateDataRange, :889-951) over the IOs that passed 1 and 2: if one of them
+ *    has buf_base == 0, data == 0 or is not contained in its buffer (RDMABuf.h:162: buf_base <= data
+ *    and data + length <= buf_base + buf_size, in 64-bit unsigned sums; a sum that wraps counts as not
+ *    contained), every one of them gets 7002 and nothing is sent: the batch is poisoned.  The
+ *    overlap check behind check_overlapping_write_buffers (default false) stays with the host.
+ * 4. The checksum of a sent IO (sendWriteRequest, :1878-1896): with HF3FS_CLIENT_WRITE_VERIFY
+ *    {type, raw CRC of data[0, length)}, for length 0 {type, ~0u} with no byte read; without it
+ *    {NONE, 0} and no data byte is read.  send_inline = (length <= max_inline_bytes) (:1898-1901).
+ *    An IO that is not sent gets {NONE, 0} and send_inline 0.
+ *
+ * Reads: only the payload of an IO that is valid by itself (it passes 1 and 2, data and buf_base are
+ * not 0, it is contained) is ever read, and only with VERIFY; it may be read although another IO
+ * poisons the batch.  No other address is read, and no store goes to a data buffer.
+ *
+ * d_updates, when not NULL, receives the request as the server's record: for a sent IO payload =
+ * data, offset, length, update_type = HF3FS_UPDATE_WRITE, write_checksum_type, write_checksum and
+ * flags = 0; for an IO that is not sent update_type = 0 only (hf3fs_crc_update_batch answers 3 and
+ * touches nothing).  No other byte of the record is stored: the chunk's address and state are the
+ * server's.  d_info[HF3FS_CLIENT_WRITE_INFO_*] is set, not accumulated. */
+int hf3fs_crc_client_write_prepare(uint8_t type, hf3fs_crc_client_write_io *d_ios, uint64_t n, uint32_t max_len,
+                                   uint32_t max_inline_bytes, uint32_t flags, hf3fs_crc_update_io *d_updates,
+                                   uint32_t *d_info, void *stream);
+
+/* What the client and writeFile do with the answers.  With HF3FS_CLIENT_WRITE_FROM_UPDATES an IO
+ * with status == 0 first takes its answer from d_updates[i] (status_in = status, result_len =
+ * length, result_checksum(_type) = out_checksum(_type)) and the four fields are stored into d_ios.
+ * An IO's final status is status != 0 ? status : status_in (setResultOfOp, :1922; an IO never sent
+ * arrives with 7003).
+ *
+ * Fold (FileWrapper.cc:218-248): file f owns IOs [d_file_off[f], d_file_off[f+1]) (ascending,
+ * clamped to n); NULL d_file_off with n_files == 0 skips it.  In file order: a final status != 0
+ * ends the fold with that code; result_checksum_type > CRC32 ends it with 3; result_len != length
+ * with 33; else ChecksumInfo::combine (Common.h:179-198): an accumulator typed otherwise than the
+ * answer ends it with 4080 (also for result_len 0), result_len 0 changes nothing, a NONE
+ * accumulator adopts the answer, else the CRC combine; result_len is added to `length`.  The
+ * answer's checksum is the CHUNK's after the update, so the fold is the CRC of the written bytes
+ * only when every IO starts its chunk.  A file whose fold ended gets length 0, {NONE, 0}, the code
+ * and failed_io; a file without IOs {0, 0, NONE, status 0}.  d_expected[f], when given
+ * (Bench.cc:41-48): a file with status 0 and value != d_expected[f] gets 7015, failed_io ~0u.
+ * max_ios_per_file >= every file's IO count chooses the schedule (one lane or one wave per file);
+ * the records are the same under either.
+ *
+ * d_failed, when given, is the ascending list of the IOs whose final status is not 0, written up
+ * to failed_cap entries; d_info[HF3FS_CLIENT_WRITE_DONE_FAILED] is their full count.
+ *
+ * Both calls: HF3FS_CRC_INVALID_ARG before a device is touched for a type other than CRC32C /
+ * CRC32, unknown flag bits, null d_ios with n > 0, null d_info, a count above 2^30,
+ * FROM_UPDATES without d_updates, n_files > 0 with null d_file_off or null d_files, failed_cap > 0
+ * with null d_failed.  n == 0 only sets d_info, and the file records when there are files.
+ * Asynchronous on `stream`, no host synchronisation, nothing read back; capturable, also as the
+ * process's first library calls, and a replayed graph works from what the records hold at replay
+ * time. */
+int hf3fs_crc_client_write_complete(hf3fs_crc_client_write_io *d_ios, uint64_t n, const uint64_t *d_file_off,
+                                    uint64_t n_files, uint64_t max_ios_per_file, uint32_t flags,
+                                    const hf3fs_crc_update_io *d_updates, const uint32_t *d_expected,
+                                    hf3fs_crc_client_write_file *d_files, uint32_t *d_failed, uint64_t failed_cap,
+                                    uint32_t *d_info, void *stream);
+/* Bytes of library-owned scratch either call takes for n IOs (the larger of the two, so the pair's
+ * buffer never grows between them); 0 for rejected counts. */
+size_t hf3fs_crc_client_write_scratch_bytes(uint64_t n, uint64_t n_files);
+
+/* ------------------------------------------------------------------------ */
 /* chain forwarding: the hop between a target's local update and its commit   */
 /* ------------------------------------------------------------------------ */
 /* One update on a head or middle target between its local update and its commit:
