@@ -471,6 +471,12 @@ struct ByteRuns {
   bool placed;  // bal / boff already placed on the stream (update prep's runs workgroup)
   uint32_t rep = 1;  // runs per wave (Plan::run_rep): bal / boff hold rep x W + 1 entries
 };
+// The tables of nw runs, not placed yet: partial[blocks], boff[nw + 1] in room for twice as many, bal[nw + 1].
+constexpr size_t byte_runs_bytes(size_t blocks, size_t nw) { return (blocks + 2 * (nw + 1)) * 8 + (nw + 1) * 4; }
+ByteRuns byte_runs_carve(void* base, uint32_t blocks, uint32_t nw, uint32_t rep) {
+  uint64_t* partial = (uint64_t*)base;
+  return {partial, (uint32_t*)(partial + blocks + 2 * (nw + 1)), partial + blocks, blocks, false, rep};
+}
 
 // zeroed_queue: the caller zeroed `out` and hands over a zeroed ticket counter
 // (update_batch: one zeroing launch per call instead of two per hash pass).
@@ -521,46 +527,53 @@ constexpr uint64_t kRecordRunsBytes = 1ull << 30;
 constexpr uint32_t kRecordRunsMinLen = 64 << 10;
 constexpr uint64_t kRunWindowBytes = 4ull << 20;  // most bytes of one byte run (create_strided)
 
+// What the carve takes without the caller's tail: {ctl[4], addr[n], len[n], v[n]} up to a multiple
+// of 64 (the head), the byte-run tables of rblocks blocks and nw runs (with_runs), 64 spare bytes.
+constexpr size_t record_head_bytes(uint64_t n) { return (16 + n * (8 + 8 + 4) + 63) / 64 * 64; }
+constexpr size_t record_own_bytes(uint64_t n, size_t rblocks, size_t nw, bool with_runs) {
+  return record_head_bytes(n) + (with_runs ? byte_runs_bytes(rblocks, nw) : 0) + 64;
+}
+// The public *_scratch_bytes functions size the tables for any device: kRunBlocksMax blocks and the
+// 16,384 waves of 1024 CUs.
+constexpr size_t kSizingWaves = 1024 * kWaves;
+
+struct RecordOptions {
+  const char* what;           // the call's name in an error
+  bool runs_ok = false;       // a large batch hashes as byte runs
+  bool reserve_runs = false;  // the byte-run tables are part of the size whatever max_len is, so that
+                              // the pair's buffer depends on n alone
+  size_t tail_bytes = 0;      // the caller's bytes behind the carve, for its fin (own is a multiple of 4),
+  void** tail = nullptr;      // and where they start
+};
 template <class Prep, class Fin>
-int run_record_jobs(Context* c, uint8_t type, uint64_t n, uint32_t max_len, uint32_t start, hipStream_t s,
-                    Prep prep, Fin fin, const char* what, bool runs_ok = false, size_t tail_bytes = 0,
-                    void** tail = nullptr, bool reserve_runs = false) {
-  const bool use_runs = runs_ok && max_len >= kRecordRunsMinLen && n * (uint64_t)max_len >= kRecordRunsBytes;
+int run_record_jobs(Context* c, uint8_t type, uint64_t n, uint32_t max_len, hipStream_t s, Prep prep, Fin fin,
+                    const RecordOptions& o) {
+  const bool use_runs = o.runs_ok && max_len >= kRecordRunsMinLen && n * (uint64_t)max_len >= kRecordRunsBytes;
   const uint32_t nw = (uint32_t)c->cus * kWaves;
   const uint32_t rblocks = (uint32_t)std::min<uint64_t>(kRunBlocksMax, std::max<uint64_t>(1, n / 256));
-  const size_t head = (16 + n * (8 + 8 + 4) + 63) / 64 * 64;
-  // reserve_runs: the byte-run tables are part of the size whatever max_len is, so that the pair's
-  // buffer depends on n alone.  The tail: the caller's, for its fin (own is a multiple of 4).
-  const size_t own = head + (use_runs || reserve_runs ? (rblocks + 2 * (nw + 1)) * 8 + (nw + 1) * 4 : 0) + 64;
-  const size_t bytes = own + tail_bytes;
+  const size_t own = record_own_bytes(n, rblocks, nw, use_runs || o.reserve_runs);
   void* scratch = nullptr;
-  if (int rc = call_scratch(c, s, bytes, &scratch)) return rc;
+  if (int rc = call_scratch(c, s, own + o.tail_bytes, &scratch)) return rc;
   uint8_t* base = (uint8_t*)scratch;
-  if (tail) *tail = base + (own + 15) / 16 * 16;
+  if (o.tail) *o.tail = base + (own + 15) / 16 * 16;
   uint32_t* maxl = (uint32_t*)base;
   uint64_t* addr = (uint64_t*)(base + 16);
   uint64_t* len = addr + n;
   uint32_t* v = (uint32_t*)(len + n);
-  int rc = HF3FS_CRC_OK;
   hipError_t e = launch_zero_words(maxl, 4, s);
   if (e == hipSuccess) e = prep(addr, len, maxl);
   if (e == hipSuccess && use_runs) e = launch_zero_words(v, n, s);  // the runs xor their parts in
-  if (e != hipSuccess) rc = fail(HF3FS_CRC_DEVICE_ERROR, "%s prep: %s", what, hipGetErrorString(e));
-  if (!rc) {
-    ListSource src{addr, len, nullptr, n, start};
-    if (use_runs) {
-      uint64_t* partial = (uint64_t*)(base + head);
-      const ByteRuns runs{partial, (uint32_t*)(partial + rblocks + 2 * (nw + 1)), partial + rblocks, rblocks, false};
-      rc = run_ranges_list(c, type, src, max_len, v, s, 0, maxl, nullptr, nullptr, &runs);
-    } else {
-      rc = run_ranges_list(c, type, src, max_len, v, s, 0, maxl);
-    }
-  }
-  if (!rc) {
-    e = fin(v);
-    if (e != hipSuccess) rc = fail(HF3FS_CRC_DEVICE_ERROR, "%s finalize: %s", what, hipGetErrorString(e));
-  }
-  return rc;
+  if (e != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "%s prep: %s", o.what, hipGetErrorString(e));
+  const ListSource src{addr, len, nullptr, n, ~0u};
+  const ByteRuns runs = use_runs ? byte_runs_carve(base + record_head_bytes(n), rblocks, nw, 1) : ByteRuns{};
+  if (int rc = run_ranges_list(c, type, src, max_len, v, s, 0, maxl, nullptr, nullptr, use_runs ? &runs : nullptr))
+    return rc;
+  if ((e = fin(v)) != hipSuccess) return fail(HF3FS_CRC_DEVICE_ERROR, "%s finalize: %s", o.what, hipGetErrorString(e));
+  return HF3FS_CRC_OK;
+}
+int record_type(uint8_t type) {  // the record batches hash with one of the two CRCs
+  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  return HF3FS_CRC_OK;
 }
 
 int create_host_staged(Context* c, uint8_t type, const void* const* h_bufs, const uint64_t* h_lens,
@@ -714,9 +727,8 @@ int hf3fs_crc_create_batch(uint8_t type, const void* const* d_bufs, const uint64
     const uint32_t nw = (uint32_t)c->cus * kWaves * rep;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(kRunBlocksMax, std::max<uint64_t>(1, n / 256));
     void* scr = nullptr;
-    if (int rc = call_scratch(c, s, (blocks + 2 * (nw + 1)) * 8 + (nw + 1) * 4, &scr)) return rc;
-    uint64_t* partial = (uint64_t*)scr;
-    const ByteRuns runs{partial, (uint32_t*)(partial + blocks + 2 * (nw + 1)), partial + blocks, blocks, false, rep};
+    if (int rc = call_scratch(c, s, byte_runs_bytes(blocks, nw), &scr)) return rc;
+    const ByteRuns runs = byte_runs_carve(scr, blocks, nw, rep);
     HIP_OR_FAIL(launch_zero_words(d_out, n, s));
     return run_ranges_list(c, type, src, max_len, d_out, s, 0, nullptr, nullptr, nullptr, &runs);
   }
@@ -1101,6 +1113,51 @@ static int ordered_args(uint8_t type, int mode, uint32_t max_rounds) {
   return HF3FS_CRC_OK;
 }
 constexpr uint64_t kOrderedMaxIos = 1ull << 30;  // 32-bit IO indices, a table of 2 n slots
+// The gate of the round calls (ordered, versioned, engine) behind their argument check: an empty
+// queue zeroes the call's info words and leaves *c null.
+static int rounds_gate(const void* d_ios, uint64_t n, uint32_t* d_info, uint32_t info_words, hipStream_t s, Context** c) {
+  *c = nullptr;
+  if (n == 0) {
+    if (d_info) HIP_OR_FAIL(launch_zero_words(d_info, info_words, s));
+    return HF3FS_CRC_OK;
+  }
+  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
+  if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
+  return get_context(c);
+}
+// Round 0 is planned like an update_batch of the n records (with every chunk distinct it IS that
+// call), on a hint word of its own: what an ordered call counts never sizes the grid of a plain
+// update_batch on the same pair.  Later rounds shrink fast and are padded to n records, so a
+// pieces-per-IO figure says nothing about them: they take the ticketed apply, which needs none.
+static UpdatePlan later_rounds(UpdatePlan p, const Context* c) {
+  p.one_shot = false;
+  p.ptab_cap = 0;
+  p.hint = nullptr;
+  p.grid = (uint32_t)c->cus * 8;
+  return p;
+}
+// The planner, then rounds 0 .. max_rounds - 1 -- the entry point's step(r), then one pass of the
+// pipeline over the round's records (os.round) on the scratch at base -- and step(max_rounds).
+extern "C++" template <class Step>
+int run_rounds(Context* c, uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t n, uint32_t max_len, int mode,
+               uint32_t max_rounds, const UpdatePlan& first, const UpdatePlan& later, const OrderScratch& os, void* base,
+               hipStream_t s, Step step) {
+  HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
+  for (uint32_t r = 0; r < max_rounds; ++r) {
+    HIP_OR_FAIL(step(r));
+    if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
+  }
+  HIP_OR_FAIL(step(max_rounds));
+  return HF3FS_CRC_OK;
+}
+// The payloads of the jobs a versioned or engine call refused behind the verify's place (4080 goes
+// first).  Every other entry of the list is empty; with no such job the pass finds a length bound of 0.
+static int hash_refused(Context* c, uint8_t type, const VersionScratch& v, uint64_t n, uint32_t max_len,
+                        const OrderScratch& os, hipStream_t s) {
+  const ListSource late{v.vaddr, v.vlen, nullptr, n, ~0u};
+  return run_ranges_list(c, type == kTypeNone ? kTypeCrc32c : type, late, max_len, v.vout, s, 0, os.ctl + kOrdVerMaxLen,
+                         nullptr, os.ctl + kOrdVerQueue);
+}
 
 size_t hf3fs_crc_update_ordered_scratch_bytes(uint64_t n, uint32_t max_len, int mode, uint32_t max_rounds) {
   if (ordered_args(kTypeCrc32c, mode, max_rounds) || n == 0 || n > kOrderedMaxIos) return 0;
@@ -1115,37 +1172,19 @@ int hf3fs_crc_update_ordered(uint8_t type, hf3fs_crc_update_io* d_ios, uint64_t 
                              uint32_t max_rounds, uint32_t* d_info, void* stream) {
   if (int rc = ordered_args(type, mode, max_rounds)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
-    if (d_info) HIP_OR_FAIL(launch_zero_words(d_info, 2, s));
-    return HF3FS_CRC_OK;
-  }
-  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
-  if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
   Context* c = nullptr;
-  if (int rc = get_context(&c)) return rc;
-  // Round 0 is planned like an update_batch of the n records (with every chunk distinct it IS that
-  // call), on a hint word of its own: what an ordered call counts never sizes the grid of a plain
-  // update_batch on the same pair.  Later rounds shrink fast and are padded to n records, so a
-  // pieces-per-IO figure says nothing about them: they take the ticketed apply, which needs none.
+  if (const int rc = rounds_gate(d_ios, n, d_info, 2, s, &c); rc || !c) return rc;
   UpdatePlan first;
   if (int rc = plan_update(c, kEntryOrdered, n, max_len, mode, nullptr, &s, &first)) return rc;
-  UpdatePlan later = first;
-  later.one_shot = false;
-  later.ptab_cap = 0;
-  later.hint = nullptr;
-  later.grid = (uint32_t)c->cus * 8;
   const size_t pipe_bytes = ordered_pipeline_bytes(first, n);
   void* base = nullptr;
   if (int rc = call_scratch(c, s, pipe_bytes + order_scratch_bytes(n), &base)) return rc;
   OrderScratch os;
   order_scratch_carve((uint8_t*)base + pipe_bytes, n, &os);
-  HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
-  for (uint32_t r = 0; r < max_rounds; ++r) {
-    HIP_OR_FAIL(launch_order_step(d_ios, n, r, max_rounds, os, nullptr, s));
-    if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
-  }
-  HIP_OR_FAIL(launch_order_step(d_ios, n, max_rounds, max_rounds, os, d_info, s));
-  return HF3FS_CRC_OK;
+  const auto step = [&](uint32_t r) {
+    return launch_order_step(d_ios, n, r, max_rounds, os, r < max_rounds ? nullptr : d_info, s);
+  };
+  return run_rounds(c, type, d_ios, n, max_len, mode, max_rounds, first, later_rounds(first, c), os, base, s, step);
 }
 
 // update_ordered with the version ladders (version_kernels.h).  Round 0 plans on the ordered
@@ -1163,21 +1202,10 @@ int hf3fs_crc_update_versioned(uint8_t type, hf3fs_crc_update_io* d_ios, hf3fs_c
   if (!d_ver) return hf3fs_crc_update_ordered(type, d_ios, n, max_len, mode, max_rounds, d_info, stream);
   if (int rc = ordered_args(type, mode, max_rounds)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
-    if (d_info) HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_VER_INFO_WORDS, s));
-    return HF3FS_CRC_OK;
-  }
-  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
-  if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
   Context* c = nullptr;
-  if (int rc = get_context(&c)) return rc;
+  if (const int rc = rounds_gate(d_ios, n, d_info, HF3FS_VER_INFO_WORDS, s, &c); rc || !c) return rc;
   UpdatePlan first;
   if (int rc = plan_update(c, kEntryOrdered, n, max_len, mode, nullptr, &s, &first)) return rc;
-  UpdatePlan later = first;  // (as in update_ordered: later rounds take the ticketed apply)
-  later.one_shot = false;
-  later.ptab_cap = 0;
-  later.hint = nullptr;
-  later.grid = (uint32_t)c->cus * 8;
   const size_t pipe_bytes = ordered_pipeline_bytes(first, n), order_bytes = versioned_order_bytes(n);
   void* base = nullptr;
   if (int rc = call_scratch(c, s, pipe_bytes + order_bytes + version_scratch_bytes(n), &base)) return rc;
@@ -1185,18 +1213,12 @@ int hf3fs_crc_update_versioned(uint8_t type, hf3fs_crc_update_io* d_ios, hf3fs_c
   VersionScratch vs;
   order_scratch_carve((uint8_t*)base + pipe_bytes, n, &os);
   version_scratch_carve((uint8_t*)base + pipe_bytes + order_bytes, n, &vs);
-  HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
-  for (uint32_t r = 0; r < max_rounds; ++r) {
-    HIP_OR_FAIL(launch_version_step(d_ios, d_ver, n, r, max_rounds, max_len, type, mode, os, vs, d_info, s));
-    if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
-  }
-  HIP_OR_FAIL(launch_version_step(d_ios, d_ver, n, max_rounds, max_rounds, max_len, type, mode, os, vs, d_info, s));
-  // The payloads of the jobs the version rungs refused: 4080 goes first (ChunkReplica.cc:193-207).
-  // Every other entry of the list is empty; with no such job the pass finds a length bound of 0.
-  const ListSource late{vs.vaddr, vs.vlen, nullptr, n, ~0u};
-  if (int rc = run_ranges_list(c, type == kTypeNone ? kTypeCrc32c : type, late, max_len, vs.vout, s, 0,
-                               os.ctl + kOrdVerMaxLen, nullptr, os.ctl + kOrdVerQueue))
+  const auto step = [&](uint32_t r) {
+    return launch_version_step(d_ios, d_ver, n, r, max_rounds, max_len, type, mode, os, vs, d_info, s);
+  };
+  if (int rc = run_rounds(c, type, d_ios, n, max_len, mode, max_rounds, first, later_rounds(first, c), os, base, s, step))
     return rc;
+  if (int rc = hash_refused(c, type, vs, n, max_len, os, s)) return rc;  // (ChunkReplica.cc:193-207)
   HIP_OR_FAIL(launch_version_settle(d_ios, n, max_rounds, os, vs, d_info, s));
   return HF3FS_CRC_OK;
 }
@@ -1229,15 +1251,9 @@ int hf3fs_crc_update_engine(uint8_t type, hf3fs_crc_update_io* d_ios, hf3fs_crc_
                             uint32_t max_len, int mode, uint32_t max_rounds, uint32_t* d_info, void* stream) {
   if (int rc = engine_args(type, mode, max_rounds)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
-    if (d_info) HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_ENGINE_INFO_WORDS, s));
-    return HF3FS_CRC_OK;
-  }
-  if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
-  if (!d_jobs) return fail(HF3FS_CRC_INVALID_ARG, "null jobs");
-  if (n > kOrderedMaxIos) return fail(HF3FS_CRC_INVALID_ARG, "too many IOs (%llu)", (unsigned long long)n);
+  if (n && d_ios && !d_jobs) return fail(HF3FS_CRC_INVALID_ARG, "null jobs");
   Context* c = nullptr;
-  if (int rc = get_context(&c)) return rc;
+  if (const int rc = rounds_gate(d_ios, n, d_info, HF3FS_ENGINE_INFO_WORDS, s, &c); rc || !c) return rc;
   const size_t order_bytes = versioned_order_bytes(n);
   UpdatePlan first;
   if (int rc = plan_update(c, kEntryEngine, n, max_len, mode, nullptr, &s, &first)) return rc;
@@ -1251,17 +1267,11 @@ int hf3fs_crc_update_engine(uint8_t type, hf3fs_crc_update_io* d_ios, hf3fs_crc_
   first.dst = es.rdst;
   UpdatePlan later = first;
   later.hint = nullptr;
-  HIP_OR_FAIL(launch_order_plan(d_ios, n, max_rounds, os, s));
-  for (uint32_t r = 0; r < max_rounds; ++r) {
-    HIP_OR_FAIL(launch_engine_step(d_ios, d_jobs, n, r, max_rounds, max_len, mode, os, es, d_info, s));
-    if (int rc = update_run(c, type, os.round, n, max_len, mode, r ? later : first, base, s)) return rc;
-  }
-  HIP_OR_FAIL(launch_engine_step(d_ios, d_jobs, n, max_rounds, max_rounds, max_len, mode, os, es, d_info, s));
-  // The payloads of the jobs refused after the verify's place: 4080 goes first (engine.rs:297-311).
-  const ListSource late{es.v.vaddr, es.v.vlen, nullptr, n, ~0u};
-  if (int rc = run_ranges_list(c, kTypeCrc32c, late, max_len, es.v.vout, s, 0, os.ctl + kOrdVerMaxLen, nullptr,
-                               os.ctl + kOrdVerQueue))
-    return rc;
+  const auto step = [&](uint32_t r) {
+    return launch_engine_step(d_ios, d_jobs, n, r, max_rounds, max_len, mode, os, es, d_info, s);
+  };
+  if (int rc = run_rounds(c, type, d_ios, n, max_len, mode, max_rounds, first, later, os, base, s, step)) return rc;
+  if (int rc = hash_refused(c, type, es.v, n, max_len, os, s)) return rc;  // (engine.rs:297-311)
   HIP_OR_FAIL(launch_engine_settle(d_ios, d_jobs, n, max_rounds, os, es, d_info, s));
   return HF3FS_CRC_OK;
 }
@@ -1304,33 +1314,32 @@ int hf3fs_crc_pair_scratch_stats(void* stream, uint64_t* call_bytes, uint64_t* a
 
 int hf3fs_crc_read_result_batch(uint8_t type, hf3fs_crc_read_io* d_ios, uint64_t n, uint32_t max_len,
                                 void* stream) {
-  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (int rc = record_type(type)) return rc;
   if (n == 0) return HF3FS_CRC_OK;
   if (!d_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
   Context* c = nullptr;
   if (int rc = get_context(&c)) return rc;
   hipStream_t s = (hipStream_t)stream;
   return run_record_jobs(
-      c, type, n, max_len, ~0u, s,
+      c, type, n, max_len, s,
       [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
         return launch_read_prep(d_ios, n, type, max_len, addr, len, maxl, s);
       },
-      [&](const uint32_t* v) { return launch_read_finalize(d_ios, n, v, s); }, "read");
+      [&](const uint32_t* v) { return launch_read_finalize(d_ios, n, v, s); }, {.what = "read"});
 }
 
 size_t hf3fs_crc_client_read_scratch_bytes(uint64_t n_ios, uint64_t n_parents) {
   if (n_ios > kClientMaxCount || n_parents > kClientMaxCount) return 0;
-  // run_record_jobs' carve {maxl[4], addr[n], len[n], v[n]}, as the pair's buffer is sized by a
-  // first call (a captured call's own memory is the exact bytes); the parents take no scratch.
-  const size_t bytes = (16 + (size_t)n_ios * (8 + 8 + 4) + 63) / 64 * 64 + 64;
-  return roomy_words((bytes + 3) / 4) * 4;
+  // run_record_jobs' carve without byte runs, as the pair's buffer is sized by a first call (a
+  // captured call's own memory is the exact bytes); the parents take no scratch.
+  return roomy_words((record_own_bytes(n_ios, 0, 0, false) + 3) / 4) * 4;
 }
 
 int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io* d_ios, uint64_t n_ios,
                                 const uint64_t* d_parent_off, uint64_t n_parents, uint64_t max_children,
                                 uint32_t max_len, uint32_t flags, hf3fs_crc_client_read_result* d_parents,
                                 hf3fs_crc_block_digest* d_blocks, uint32_t* d_info, void* stream) {
-  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (int rc = record_type(type)) return rc;
   if (flags & ~(uint32_t)HF3FS_CLIENT_READ_VERIFY) return fail(HF3FS_CRC_INVALID_ARG, "unknown flags %#x", flags);
   if (!d_ios && n_ios) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
   if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
@@ -1357,32 +1366,25 @@ int hf3fs_crc_client_read_batch(uint8_t type, hf3fs_crc_client_read_io* d_ios, u
     return HF3FS_CRC_OK;
   }
   return run_record_jobs(
-      c, type, n_ios, max_len, ~0u, s,
+      c, type, n_ios, max_len, s,
       [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
         return launch_client_read_prep(d_ios, n_ios, type, max_len, addr, len, maxl, s);
       },
-      merge, "client read");
+      merge, {.what = "client read"});
 }
 
-// Prepare takes run_record_jobs' carve {ctl[4], addr[n], len[n], v[n]} with the byte-run tables
-// reserved (their size depends on the device: bounded here by kRunBlocksMax and 4096 waves),
-// complete client_write_scratch_bytes; a caller sizes for the larger.
-static size_t client_write_call_bytes(uint64_t n) {
-  const size_t head = (16 + (size_t)n * (8 + 8 + 4) + 63) / 64 * 64 + 64;
-  constexpr size_t nw = 1024 * kWaves;  // (a device of 1024 CUs)
-  constexpr size_t runs = (kRunBlocksMax + 2 * (nw + 1)) * 8 + (nw + 1) * 4;
-  return std::max(head + runs, client_write_scratch_bytes(n) + 16);
-}
-
+// Prepare takes run_record_jobs' carve with the byte-run tables reserved, complete
+// client_write_scratch_bytes; a caller sizes for the larger.  The files take no scratch.
 size_t hf3fs_crc_client_write_scratch_bytes(uint64_t n, uint64_t n_files) {
   if (n > kClientWriteMaxCount || n_files > kClientWriteMaxCount) return 0;
-  return roomy_words((client_write_call_bytes(n) + 3) / 4) * 4;  // (the files take no scratch)
+  const size_t prepare = record_own_bytes(n, kRunBlocksMax, kSizingWaves, true);
+  return roomy_words((std::max(prepare, client_write_scratch_bytes(n) + 16) + 3) / 4) * 4;
 }
 
 int hf3fs_crc_client_write_prepare(uint8_t type, hf3fs_crc_client_write_io* d_ios, uint64_t n, uint32_t max_len,
                                    uint32_t max_inline_bytes, uint32_t flags, hf3fs_crc_update_io* d_updates,
                                    uint32_t* d_info, void* stream) {
-  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (int rc = record_type(type)) return rc;
   if (flags & ~(uint32_t)HF3FS_CLIENT_WRITE_VERIFY) return fail(HF3FS_CRC_INVALID_ARG, "unknown flags %#x", flags);
   if (!d_ios && n) return fail(HF3FS_CRC_INVALID_ARG, "null ios");
   if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
@@ -1415,12 +1417,12 @@ int hf3fs_crc_client_write_prepare(uint8_t type, hf3fs_crc_client_write_io* d_io
   // planner's segment.  The run tables are reserved whatever max_len is.
   const bool runs_ok = max_len >= kClientWriteRunsMinLen;
   return run_record_jobs(
-      c, type, n, max_len, ~0u, s,
+      c, type, n, max_len, s,
       [&](uint64_t* addr, uint64_t* len, uint32_t* ctl) {
         poison = ctl + 1;  // (run_record_jobs zeroes the four words; the range kernels read ctl[0] only)
         return launch_client_write_prep(d_ios, n, max_len, true, addr, len, ctl, s);
       },
-      finish, "client write prepare", runs_ok, 0, nullptr, true);
+      finish, {.what = "client write prepare", .runs_ok = runs_ok, .reserve_runs = true});
 }
 
 int hf3fs_crc_client_write_complete(hf3fs_crc_client_write_io* d_ios, uint64_t n, const uint64_t* d_file_off,
@@ -1456,23 +1458,15 @@ int hf3fs_crc_client_write_complete(hf3fs_crc_client_write_io* d_ios, uint64_t n
   return HF3FS_CRC_OK;
 }
 
-// run_record_jobs' carve {maxl[4], addr[n], len[n], v[n]}, the byte-run tables a large prepare
-// adds (their size depends on the device: bounded here by kRunBlocksMax and 4096 waves), and
-// complete's tail.
-static size_t forward_call_bytes(uint64_t n) {
-  const size_t head = (16 + (size_t)n * (8 + 8 + 4) + 63) / 64 * 64 + 64;
-  constexpr size_t nw = 1024 * kWaves;  // (a device of 1024 CUs)
-  constexpr size_t runs = (kRunBlocksMax + 2 * (nw + 1)) * 8 + (nw + 1) * 4;
-  return head + runs + forward_scratch_bytes(n) + 16;
-}
-
+// run_record_jobs' carve with the byte-run tables a large prepare adds, and complete's tail.
 size_t hf3fs_crc_forward_scratch_bytes(uint64_t n) {
   if (n > kForwardMaxJobs) return 0;
-  return roomy_words((forward_call_bytes(n) + 3) / 4) * 4;
+  const size_t bytes = record_own_bytes(n, kRunBlocksMax, kSizingWaves, true) + forward_scratch_bytes(n) + 16;
+  return roomy_words((bytes + 3) / 4) * 4;
 }
 
 static int forward_args(uint8_t type, const hf3fs_crc_forward_job* d_jobs, uint64_t n, const uint32_t* d_info) {
-  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (int rc = record_type(type)) return rc;
   if (!d_jobs && n) return fail(HF3FS_CRC_INVALID_ARG, "null jobs");
   if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
   if (n > kForwardMaxJobs) return fail(HF3FS_CRC_INVALID_ARG, "too many jobs (%llu)", (unsigned long long)n);
@@ -1491,14 +1485,14 @@ int hf3fs_crc_forward_prepare(uint8_t type, hf3fs_crc_forward_job* d_jobs, uint6
   // is complete's and the run tables are reserved in both calls, so that either call takes the same
   // bytes for n jobs whatever max_len is: the pair's buffer never grows between the two.
   return run_record_jobs(
-      c, type, n, max_len, ~0u, s,
+      c, type, n, max_len, s,
       [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
         return launch_forward_prep(d_jobs, n, type, max_len, false, addr, len, maxl, s);
       },
       [&](const uint32_t* v) {
         return launch_forward_prepare_finish(d_jobs, n, type, max_len, max_inline_bytes, v, d_info, s);
       },
-      "forward prepare", true, forward_scratch_bytes(n) + 16, nullptr, true);
+      {.what = "forward prepare", .runs_ok = true, .reserve_runs = true, .tail_bytes = forward_scratch_bytes(n) + 16});
 }
 
 int hf3fs_crc_forward_complete(uint8_t type, hf3fs_crc_forward_job* d_jobs, uint64_t n, uint32_t max_len,
@@ -1511,7 +1505,7 @@ int hf3fs_crc_forward_complete(uint8_t type, hf3fs_crc_forward_job* d_jobs, uint
   if (n == 0) return HF3FS_CRC_OK;
   void* tail = nullptr;
   return run_record_jobs(
-      c, type, n, max_len, ~0u, s,
+      c, type, n, max_len, s,
       [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
         return launch_forward_prep(d_jobs, n, type, max_len, true, addr, len, maxl, s);
       },
@@ -1520,12 +1514,12 @@ int hf3fs_crc_forward_complete(uint8_t type, hf3fs_crc_forward_job* d_jobs, uint
         forward_scratch_carve(tail, n, &fs);
         return launch_forward_complete_finish(d_jobs, n, type, max_len, v, d_commit_idx, d_info, fs, s);
       },
-      "forward complete", false, forward_scratch_bytes(n) + 16, &tail, true);
+      {.what = "forward complete", .reserve_runs = true, .tail_bytes = forward_scratch_bytes(n) + 16, .tail = &tail});
 }
 
 int hf3fs_crc_scrub_batch(uint8_t type, hf3fs_crc_scrub_io* d_ios, uint64_t n, uint32_t max_len,
                           uint32_t* d_mismatch_count, void* stream) {
-  if (type != kTypeCrc32c && type != kTypeCrc32) return fail(HF3FS_CRC_INVALID_ARG, "type must be CRC32C or CRC32");
+  if (int rc = record_type(type)) return rc;
   if (!d_mismatch_count) return fail(HF3FS_CRC_INVALID_ARG, "null mismatch count");
   hipStream_t s = (hipStream_t)stream;
   HIP_OR_FAIL(launch_zero_words(d_mismatch_count, 1, s));
@@ -1534,11 +1528,11 @@ int hf3fs_crc_scrub_batch(uint8_t type, hf3fs_crc_scrub_io* d_ios, uint64_t n, u
   Context* c = nullptr;
   if (int rc = get_context(&c)) return rc;
   return run_record_jobs(
-      c, type, n, max_len, ~0u, s,
-      [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
+      c, type, n, max_len, s, [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
         return launch_scrub_prep(d_ios, n, type, max_len, addr, len, maxl, s);
       },
-      [&](const uint32_t* v) { return launch_scrub_finalize(d_ios, n, v, d_mismatch_count, s); }, "scrub", true);
+      [&](const uint32_t* v) { return launch_scrub_finalize(d_ios, n, v, d_mismatch_count, s); },
+      {.what = "scrub", .runs_ok = true});
 }
 
 size_t hf3fs_crc_sync_plan_scratch_bytes(uint64_t n_local, uint64_t n_remote) {

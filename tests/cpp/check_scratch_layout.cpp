@@ -5,6 +5,8 @@
 // aligned base and every member must be 16-byte aligned, disjoint from the others and inside
 // [base, base + *_scratch_bytes).  A member that outgrows the slack term of its size fails here
 // instead of becoming a kernel that writes past the pair's buffer.
+// Cover: the public sizes of the record batches (client read, client write, forward) are at least
+// what a call takes on a device of 256 CUs, restated here.
 // Sizes: "size <key> <value>" lines, compared by tests/test_scratch_layout.py with
 // tests/golden/scratch_sizes.json.
 #include <algorithm>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "../../include/hf3fs_crc.h"
+#include "../../3fs_amd/csrc/client_write_kernels.h"
 #include "../../3fs_amd/csrc/digest_kernels.h"
 #include "../../3fs_amd/csrc/engine_kernels.h"
 #include "../../3fs_amd/csrc/forward_kernels.h"
@@ -161,10 +164,34 @@ void check_n(uint64_t n) {
       size_line(key("digest_scratch_bytes", n, splits, fill), digest_scratch_bytes(n, splits, fill != 0));
 }
 
+// The public sizes of the record batches cover what a call of n records takes on a device of 256
+// CUs.  The need is restated here, independently of the library: the carve {ctl[4], addr[n],
+// len[n], v[n]} up to a multiple of 64, the byte-run tables of min(kRunBlocksMax, max(1, n / 256))
+// blocks and nw waves where the call reserves them, 64 spare bytes, and the caller's tail.
+void check_record_cover(uint64_t n) {
+  const size_t nw = 256 * kWaves, blocks = std::min<uint64_t>(kRunBlocksMax, std::max<uint64_t>(1, n / 256));
+  const size_t plain = (16 + n * (8 + 8 + 4) + 63) / 64 * 64 + 64;
+  const size_t with_runs = plain + (blocks + 2 * (nw + 1)) * 8 + (nw + 1) * 4;
+  const struct {
+    const char* name;
+    size_t pub, need;
+  } sizes[] = {{"client_read", hf3fs_crc_client_read_scratch_bytes(n, n), plain},
+               {"client_write", hf3fs_crc_client_write_scratch_bytes(n, n), with_runs},
+               {"forward", hf3fs_crc_forward_scratch_bytes(n), with_runs + forward_scratch_bytes(n) + 16}};
+  for (const auto& x : sizes)
+    if (x.pub < x.need)
+      ++g_failures, fprintf(stderr, "n %llu: hf3fs_crc_%s_scratch_bytes is %zu, a call takes %zu\n",
+                            (unsigned long long)n, x.name, x.pub, x.need);
+  size_line(key("client_write_scratch_bytes", n), client_write_scratch_bytes(n));
+  size_line(key("hf3fs_crc_client_write_scratch_bytes", n), hf3fs_crc_client_write_scratch_bytes(n, n));
+}
+
 }  // namespace
 
 int main() {
   for (uint64_t n : {1ull, 2ull, 3ull, 15ull, 16ull, 17ull, 255ull, 256ull, 257ull, 4096ull, 65537ull, 1000003ull}) check_n(n);
+  for (uint64_t n : {1ull, 2ull, 15ull, 16ull, 17ull, 255ull, 256ull, 257ull, 4096ull, 65537ull, 1000003ull, 1ull << 30})
+    check_record_cover(n);
   if (g_failures) return fprintf(stderr, "%d layout failures\n", g_failures), 1;
   printf("ALL OK\n");
   return 0;

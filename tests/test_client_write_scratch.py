@@ -1,9 +1,10 @@
 """The scratch carve of hf3fs_crc_client_write_complete fits its byte count and the public sizing
 function covers both calls (tests/cpp/check_client_write_scratch.cpp), a program of its own beside
-tests/cpp/check_scratch_layout.cpp: the sizes recorded in tests/golden/scratch_sizes.json are the
-other calls' and do not move.  A CPU test: the program calls only sizing and carving functions of
-libhf3fs_crc.so, on a fake base."""
+tests/cpp/check_scratch_layout.cpp, with its own restatement of what prepare takes.  The 24 sizes
+it prints are recorded in tests/golden/scratch_sizes.json and do not move.  A CPU test: the
+program calls only sizing and carving functions of libhf3fs_crc.so, on a fake base."""
 import importlib
+import json
 import os
 import shutil
 import subprocess
@@ -28,5 +29,8 @@ def test_client_write_carve_fits_and_public_size_covers(tmp_path):
     assert "ALL OK" in r.stdout
     sizes = {p[1]: int(p[2]) for p in (line.split() for line in r.stdout.splitlines()) if p[0] == "size"}
     assert len(sizes) == 24
+    with open(os.path.join(REPO, "tests", "golden", "scratch_sizes.json")) as f:
+        want = json.load(f)
+    assert sizes == {k: want[k] for k in sizes}
     pub = [sizes[f"hf3fs_crc_client_write_scratch_bytes/{n}"] for n in (1, 257, 65537, 1000003, 1 << 30)]
     assert pub == sorted(pub) and pub[0] > 0 and pub[-1] >= 20 << 30
