@@ -41,4 +41,10 @@ from ._lib import (FORWARD_COMMIT, FORWARD_DONE_NAMES, FORWARD_INFO_NAMES, FORWA
                    FORWARD_REQ_INLINE, FORWARD_REQ_SYNCING, FORWARD_RETURN, FORWARD_SEND, NO_SUCCESSOR_TARGET,
                    UPDATE_REMOVE, ForwardJob, forward_complete, forward_job_dtype, forward_prepare,
                    forward_scratch_bytes)
+from ._lib import (CHUNK_METADATA_GET_ERROR, CHUNK_METADATA_NOT_FOUND, CHUNK_NOT_COMMIT,  # noqa: F401
+                   CHUNK_READ_FAILED, RDMA_NO_BUF, SERVER_READ_BUF_BIG, SERVER_READ_BUF_NONE, SERVER_READ_BUF_SMALL,
+                   SERVER_READ_DONE_NAMES, SERVER_READ_INFO_NAMES, SERVER_READ_INFO_WORDS, SERVER_READ_NONE,
+                   SERVER_READ_XMIT_INLINE, SERVER_READ_XMIT_NONE, SERVER_READ_XMIT_RDMA, TARGET_STATE_INVALID,
+                   ServerReadJob, ServerReadReq, ServerReadWr, server_read_complete, server_read_job_dtype,
+                   server_read_prepare, server_read_req_dtype, server_read_scratch_bytes, server_read_wr_dtype)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

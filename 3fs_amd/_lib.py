@@ -275,6 +275,57 @@ FORWARD_INFO_NAMES = ("sent", "returned", "no_successor", "sync_hashed", "sync_m
 FORWARD_DONE_NAMES = ("commits", "returned", "e7015", "e4081", "e4082", "rehashed", "corrupted", "unhashable")
 
 
+class ServerReadJob(ctypes.Structure):
+    """hf3fs_crc_server_read_job: one ReadIO of the server's batchRead around its AIO
+    (StorageOperator.cc:98-226, BatchReadJob.cc:16-113, AioStatus.cc:27-55)."""
+    _fields_ = [
+        ("remote_addr", _u64c), ("inner_offset", _u64c), ("localbuf", _u64c), ("res", ctypes.c_int64),
+        ("read_offset", _u64c), ("inline_off", _u64c),
+        ("offset", _u32c), ("length", _u32c), ("rdmabuf_size", _u32c), ("rkey", _u32c),
+        ("target_status", _i32c), ("meta_status", _i32c), ("commit_ver", _u32c), ("update_ver", _u32c),
+        ("chain_ver", _u32c), ("chunk_len", _u32c), ("chunk_checksum", _u32c),
+        ("meta_status_now", _i32c), ("update_ver_now", _u32c),
+        # out of prepare
+        ("head_len", _u32c), ("tail_len", _u32c), ("read_len", _u32c), ("buf_ordinal", _u32c), ("buf_off", _u32c),
+        ("status", _i32c),
+        # out of complete
+        ("result_len", _u32c), ("result_status", _i32c), ("checksum", _u32c),
+        ("has_rkey", _u8c), ("up_to_date", _u8c), ("engine", _u8c), ("chunk_checksum_type", _u8c),
+        ("buf_kind", _u8c), ("checksum_type", _u8c), ("reserved", _u8c * 50),
+    ]
+
+
+class ServerReadReq(ctypes.Structure):
+    """hf3fs_crc_server_read_req: one BatchReadReq; it owns a contiguous range of the jobs."""
+    _fields_ = [
+        ("total_len", _u64c), ("total_head", _u64c), ("total_tail", _u64c),
+        ("inline_off", _u64c), ("inline_bytes", _u64c), ("wr_bytes", _u64c),
+        ("max_msg_sz", _u32c), ("status", _i32c), ("failed_job", _u32c), ("n_small", _u32c), ("n_big", _u32c),
+        ("n_ok", _u32c), ("wr_first", _u32c), ("wr_count", _u32c), ("wr_fails", _u32c),
+        ("checksum_type", _u8c), ("xmit", _u8c), ("read_uncommitted", _u8c), ("recalculate", _u8c),
+        ("reserved", _u8c * 40),
+    ]
+
+
+class ServerReadWr(ctypes.Structure):
+    """hf3fs_crc_server_read_wr: one RDMA write of the list (RDMAReqBatch::add's arguments)."""
+    _fields_ = [("remote_addr", _u64c), ("local_addr", _u64c), ("length", _u32c), ("rkey", _u32c), ("job", _u32c),
+                ("req", _u32c)]
+
+
+assert ctypes.sizeof(ServerReadJob) == 192 and ctypes.sizeof(ServerReadReq) == 128
+assert ctypes.sizeof(ServerReadWr) == 32
+RDMA_NO_BUF, CHUNK_METADATA_NOT_FOUND, CHUNK_METADATA_GET_ERROR, CHUNK_NOT_COMMIT = 2019, 4001, 4002, 4004
+TARGET_STATE_INVALID = 4032
+SERVER_READ_XMIT_RDMA, SERVER_READ_XMIT_INLINE, SERVER_READ_XMIT_NONE = 0, 1, 2
+SERVER_READ_BUF_NONE, SERVER_READ_BUF_SMALL, SERVER_READ_BUF_BIG = 0, 1, 2
+SERVER_READ_NONE = 0xFFFFFFFF  # ServerReadReq.failed_job: no job failed the request
+SERVER_READ_INFO_WORDS = 8
+SERVER_READ_INFO_NAMES = ("reqs_ok", "reqs_failed", "jobs_ok", "jobs_failed", "small", "big", "reserved6",
+                          "reserved7")
+SERVER_READ_DONE_NAMES = ("ok", "failed", "inline_lo", "inline_hi", "inline_overflow", "wr", "wr_fails", "hashed")
+
+
 class ScrubIO(ctypes.Structure):
     """hf3fs_crc_scrub_io: one stored chunk vs its persisted checksum."""
     _fields_ = [
@@ -438,6 +489,9 @@ SIGNATURES = {
     "hf3fs_crc_forward_prepare": (_int, [_u8, _vp, _u64, _u32, _u32, _vp, _vp]),
     "hf3fs_crc_forward_complete": (_int, [_u8, _vp, _u64, _u32, _vp, _vp, _vp]),
     "hf3fs_crc_forward_scratch_bytes": (ctypes.c_size_t, [_u64]),
+    "hf3fs_crc_server_read_prepare": (_int, [_vp, _u64, _vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp]),
+    "hf3fs_crc_server_read_complete": (_int, [_u8, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "hf3fs_crc_server_read_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
     "hf3fs_crc_file_digest_batch": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "hf3fs_crc_file_digest_batch_ex": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
     "hf3fs_crc_md5_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp]),
@@ -806,6 +860,48 @@ def forward_complete(ctype, jobs, n, info, max_len, commit_idx=None, stream=None
 def forward_scratch_bytes(n):
     """Bytes of library-owned scratch either forward call takes for n jobs (0: rejected count)."""
     return int(load().hf3fs_crc_forward_scratch_bytes(n))
+
+
+def _record_dtype(struct):
+    import numpy as np
+    kinds = {_u8c: "u1", _u32c: "<u4", _i32c: "<i4", _u64c: "<u8", ctypes.c_int64: "<i8"}
+    return np.dtype([(name, kinds[t]) if t in kinds else (name, "u1", (ctypes.sizeof(t),))
+                     for name, t in struct._fields_])
+
+
+def server_read_job_dtype():
+    """numpy dtype of hf3fs_crc_server_read_job (include/hf3fs_crc.h): one 192-byte record per ReadIO."""
+    return _record_dtype(ServerReadJob)
+
+
+def server_read_req_dtype():
+    """numpy dtype of hf3fs_crc_server_read_req: one 128-byte record per BatchReadReq."""
+    return _record_dtype(ServerReadReq)
+
+
+def server_read_wr_dtype():
+    """numpy dtype of hf3fs_crc_server_read_wr: one 32-byte entry of the RDMA write list."""
+    return _record_dtype(ServerReadWr)
+
+
+def server_read_prepare(jobs, n, reqs, req_off, n_reqs, info, small_buf, big_buf, max_jobs_per_req=0, stream=None):
+    """hf3fs_crc_server_read_prepare: jobs / reqs device arrays of the two records (the prepare
+    outputs written in place), req_off n_reqs + 1 device u64, info SERVER_READ_INFO_WORDS device u32."""
+    return check(load().hf3fs_crc_server_read_prepare(_p(jobs), n, _p(reqs), _p(req_off), n_reqs, max_jobs_per_req,
+                                                      small_buf, big_buf, _p(info), _s(stream)))
+
+
+def server_read_complete(ctype, jobs, n, reqs, req_off, n_reqs, info, max_len, inline=None, inline_cap=0, wr=None,
+                         wr_cap=0, stream=None):
+    """hf3fs_crc_server_read_complete: the complete outputs written in place, inline the response
+    arena of inline_cap bytes or None, wr wr_cap device hf3fs_crc_server_read_wr or None."""
+    return check(load().hf3fs_crc_server_read_complete(ctype, _p(jobs), n, _p(reqs), _p(req_off), n_reqs, max_len,
+                                                       _p(inline), inline_cap, _p(wr), wr_cap, _p(info), _s(stream)))
+
+
+def server_read_scratch_bytes(n, n_reqs=0):
+    """Bytes of library-owned scratch complete takes for n jobs of n_reqs requests (0: rejected counts)."""
+    return int(load().hf3fs_crc_server_read_scratch_bytes(n, n_reqs))
 
 
 MD5_INIT, MD5_FINAL = 1, 2  # hf3fs_crc_md5_batch flags

@@ -83,4 +83,32 @@ __device__ __forceinline__ void compact_scatter_share(const Take take, const uin
   }
 }
 
+// The same walk for a list of records of any kind: place(i, at, taken) is called for every record
+// i of the share, `at` the taken records before it (from base on) and so, for a taken record, its
+// place in the list.  hf3fs_crc_server_read_complete builds its RDMA write list with it and keeps
+// every record's `at` for the per-request first / count.
+template <class Take, class Place>
+__device__ __forceinline__ void compact_place_share(const Take take, const uint64_t lo, const uint64_t hi,
+                                                    uint64_t base, const Place place, uint32_t* wave_n) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (uint64_t i0 = lo; i0 < hi; i0 += 256) {  // workgroup-uniform
+    const uint64_t i = i0 + threadIdx.x;
+    const bool mine = i < hi && take(i);
+    const unsigned long long votes = __ballot(mine);
+    if (lane == 0) wave_n[wave] = (uint32_t)__popcll(votes);
+    __syncthreads();
+    uint32_t before = 0, tile = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w) {
+      const uint32_t c = wave_n[w];
+      before += w < wave ? c : 0u;
+      tile += c;
+    }
+    const uint64_t at = base + before + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
+    if (i < hi) place(i, at, mine);
+    base += tile;
+    __syncthreads();
+  }
+}
+
 }  // namespace hf3fs_crc

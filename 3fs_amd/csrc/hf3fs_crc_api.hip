@@ -36,6 +36,8 @@
 #include "md5_kernels.h"
 #include "options.h"
 #include "order_kernels.h"
+#include "server_read_kernels.h"
+#include "server_read_plan.h"  // kServerReadMaxCount
 #include "sync_kernels.h"
 #include "update_kernels.h"
 #include "update_plan.h"  // kPlanRanges
@@ -1515,6 +1517,76 @@ int hf3fs_crc_forward_complete(uint8_t type, hf3fs_crc_forward_job* d_jobs, uint
         return launch_forward_complete_finish(d_jobs, n, type, max_len, v, d_commit_idx, d_info, fs, s);
       },
       {.what = "forward complete", .reserve_runs = true, .tail_bytes = forward_scratch_bytes(n) + 16, .tail = &tail});
+}
+
+// Complete takes run_record_jobs' carve without byte runs (reaped reads keep the planner, as read
+// results do) and its own tail; prepare takes no scratch.
+size_t hf3fs_crc_server_read_scratch_bytes(uint64_t n, uint64_t n_reqs) {
+  if (n > kServerReadMaxCount || n_reqs > kServerReadMaxCount) return 0;
+  const size_t bytes = record_own_bytes(n, 0, 0, false) + server_read_scratch_bytes(n) + 16;
+  return roomy_words((bytes + 3) / 4) * 4;
+}
+
+static int server_read_args(const hf3fs_crc_server_read_job* d_jobs, uint64_t n, const hf3fs_crc_server_read_req* d_reqs,
+                            const uint64_t* d_req_off, uint64_t n_reqs, const uint32_t* d_info) {
+  if (!d_jobs && n) return fail(HF3FS_CRC_INVALID_ARG, "null jobs");
+  if ((!d_reqs || !d_req_off) && n_reqs) return fail(HF3FS_CRC_INVALID_ARG, "requests need records and offsets");
+  if (n && !n_reqs) return fail(HF3FS_CRC_INVALID_ARG, "%llu jobs of no request", (unsigned long long)n);
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if (n > kServerReadMaxCount || n_reqs > kServerReadMaxCount)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many jobs or requests (%llu, %llu)", (unsigned long long)n,
+                (unsigned long long)n_reqs);
+  return HF3FS_CRC_OK;
+}
+
+int hf3fs_crc_server_read_prepare(hf3fs_crc_server_read_job* d_jobs, uint64_t n, hf3fs_crc_server_read_req* d_reqs,
+                                  const uint64_t* d_req_off, uint64_t n_reqs, uint64_t max_jobs_per_req,
+                                  uint32_t small_buf, uint32_t big_buf, uint32_t* d_info, void* stream) {
+  if (int rc = server_read_args(d_jobs, n, d_reqs, d_req_off, n_reqs, d_info)) return rc;
+  (void)max_jobs_per_req;  // no effect at present: one lane walks one request whatever its length
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_SERVER_READ_INFO_WORDS, s));  // the kernel adds into it
+  if (n_reqs == 0) return HF3FS_CRC_OK;
+  HIP_OR_FAIL(launch_server_read_prepare(d_jobs, n, d_reqs, d_req_off, n_reqs, small_buf, big_buf, d_info, s));
+  return HF3FS_CRC_OK;
+}
+
+int hf3fs_crc_server_read_complete(uint8_t type, hf3fs_crc_server_read_job* d_jobs, uint64_t n,
+                                   hf3fs_crc_server_read_req* d_reqs, const uint64_t* d_req_off, uint64_t n_reqs,
+                                   uint32_t max_len, void* d_inline, uint64_t inline_cap,
+                                   hf3fs_crc_server_read_wr* d_wr, uint64_t wr_cap, uint32_t* d_info, void* stream) {
+  if (int rc = record_type(type)) return rc;
+  if (int rc = server_read_args(d_jobs, n, d_reqs, d_req_off, n_reqs, d_info)) return rc;
+  if (inline_cap && !d_inline) return fail(HF3FS_CRC_INVALID_ARG, "null inline arena");
+  if (wr_cap && !d_wr) return fail(HF3FS_CRC_INVALID_ARG, "null write list");
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_SERVER_READ_INFO_WORDS, s));  // the kernels add into it
+  if (n_reqs == 0) return HF3FS_CRC_OK;
+  if (n == 0) {  // requests of no job: their outputs alone
+    HIP_OR_FAIL(launch_server_read_requests(d_jobs, 0, d_reqs, d_req_off, n_reqs, ServerReadScratch{}, s));
+    return HF3FS_CRC_OK;
+  }
+  void* tail = nullptr;
+  ServerReadScratch ss;
+  return run_record_jobs(
+      c, type, n, max_len, s,
+      [&](uint64_t* addr, uint64_t* len, uint32_t* maxl) {
+        server_read_scratch_carve(tail, n, &ss);
+        return launch_server_read_prep(d_jobs, n, d_reqs, d_req_off, n_reqs, type, max_len, addr, len, maxl, ss, s);
+      },
+      [&](const uint32_t* v) {
+        hipError_t e = launch_server_read_finish(d_jobs, n, d_reqs, type, max_len, v, inline_cap, d_wr, wr_cap, d_info,
+                                                 ss, s);
+        if (e == hipSuccess) e = launch_server_read_requests(d_jobs, n, d_reqs, d_req_off, n_reqs, ss, s);
+        // The inline pack: a launch of its own behind the hash and the offsets, never fused with either.
+        if (e == hipSuccess && d_inline && inline_cap) e = launch_server_read_pack(d_jobs, n, d_inline, inline_cap, d_info, ss, s);
+        return e;
+      },
+      {.what = "server read complete", .tail_bytes = server_read_scratch_bytes(n) + 16, .tail = &tail});
 }
 
 int hf3fs_crc_scrub_batch(uint8_t type, hf3fs_crc_scrub_io* d_ios, uint64_t n, uint32_t max_len,

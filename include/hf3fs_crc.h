@@ -46,6 +46,10 @@ enum {
   HF3FS_CRC_INVALID_ARG = 3,                  /* StatusCode::kInvalidArg (:24) */
   HF3FS_CRC_INVALID_FORMAT = 33,              /* StatusCode::kInvalidFormat (:42) */
   HF3FS_CRC_SERDE_INSUFFICIENT_LENGTH = 40,   /* StatusCode::kSerdeInsufficientLength (:44) */
+  HF3FS_CRC_RDMA_NO_BUF = 2019,               /* RPCCode::kRDMANoBuf (:106) */
+  HF3FS_CRC_CHUNK_METADATA_NOT_FOUND = 4001,  /* StorageCode::kChunkMetadataNotFound (:151) */
+  HF3FS_CRC_CHUNK_METADATA_GET_ERROR = 4002,  /* StorageCode::kChunkMetadataGetError (:152) */
+  HF3FS_CRC_CHUNK_NOT_COMMIT = 4004,          /* StorageCode::kChunkNotCommit (:154) */
   HF3FS_CRC_CHUNK_NOT_CLEAN = 4005,           /* StorageCode::kChunkNotClean (:155) */
   HF3FS_CRC_CHUNK_STALE_UPDATE = 4006,        /* StorageCode::kChunkStaleUpdate (:156) */
   HF3FS_CRC_CHUNK_MISSING_UPDATE = 4007,      /* StorageCode::kChunkMissingUpdate (:157) */
@@ -54,6 +58,7 @@ enum {
   HF3FS_CRC_CHUNK_ADVANCE_UPDATE = 4012,      /* StorageCode::kChunkAdvanceUpdate (:162) */
   HF3FS_CRC_CHUNK_SIZE_MISMATCH = 4015,       /* StorageCode::kChunkSizeMismatch (:165) */
   HF3FS_CRC_CHUNK_STALE_COMMIT = 4023,        /* StorageCode::kChunkStaleCommit (:172) */
+  HF3FS_CRC_TARGET_STATE_INVALID = 4032,      /* StorageCode::kTargetStateInvalid (:176) */
   HF3FS_CRC_NO_SUCCESSOR_TARGET = 4033,       /* StorageCode::kNoSuccessorTarget (:177) */
   HF3FS_CRC_CHECKSUM_MISMATCH = 4080,         /* StorageCode::kChecksumMismatch (:186) */
   HF3FS_CRC_CHAIN_VERSION_MISMATCH = 4081,    /* StorageCode::kChainVersionMismatch (:187) */
@@ -1093,6 +1098,199 @@ int hf3fs_crc_forward_complete(uint8_t type, hf3fs_crc_forward_job *d_jobs, uint
 size_t hf3fs_crc_forward_scratch_bytes(uint64_t n);
 
 /* ------------------------------------------------------------------------ */
+/* the storage server's batchRead (StorageOperator::batchRead)  */
+/* ------------------------------------------------------------------------ */
+/* One record per ReadIO of every reaped BatchReadReq, one record per request; request r owns jobs
+ * [d_req_off[r], d_req_off[r+1]) of d_jobs (d_req_off: n_reqs + 1 non-decreasing offsets,
+ * d_req_off[0] == 0, d_req_off[n_reqs] == n; an offset above n is read as n, so no record outside
+ * the arrays is touched whatever the offsets hold).  Every decision is plain C++ in
+ * 3fs_amd/csrc/server_read_plan.h. */
+typedef struct hf3fs_crc_server_read_job {
+  /* in: ReadIO */
+  uint64_t remote_addr;    /* rdmabuf.addr() */
+  uint64_t inner_offset;   /* in, chunk at prepare: meta.innerOffset / fd_and_offset().offset */
+  /* in, completion (the host fills them when it builds the iocbs and reaps the events) */
+  uint64_t localbuf;       /* device address of the aligned read: [localbuf, +read_len) */
+  int64_t res;             /* io_event.res */
+  /* out */
+  uint64_t read_offset;    /* prepare: inner_offset + (offset - head_len) */
+  uint64_t inline_off;     /* complete: byte offset in d_inline (0 for a job that packs nothing) */
+  /* in: ReadIO */
+  uint32_t offset, length, rdmabuf_size, rkey;
+  /* in: target, chunk at prepare */
+  int32_t target_status;   /* 0, or the code of getByChainId's error */
+  int32_t meta_status;     /* 0, or the lookup's code (4001, 4002) */
+  uint32_t commit_ver;     /* in; an engine job's is overwritten by update_ver in prepare */
+  uint32_t update_ver, chain_ver, chunk_len, chunk_checksum;
+  /* in, completion */
+  int32_t meta_status_now; /* aioFinishRead's lookup */
+  uint32_t update_ver_now;
+  /* out of prepare */
+  uint32_t head_len, tail_len, read_len, buf_ordinal, buf_off;
+  int32_t status;
+  /* out of complete */
+  uint32_t result_len;
+  int32_t result_status;
+  uint32_t checksum;
+  /* in */
+  uint8_t has_rkey, up_to_date, engine, chunk_checksum_type;
+  /* out */
+  uint8_t buf_kind;        /* prepare: HF3FS_SERVER_READ_BUF_* */
+  uint8_t checksum_type;   /* complete */
+  uint8_t reserved[50];
+} hf3fs_crc_server_read_job;   /* 192 bytes */
+
+typedef struct hf3fs_crc_server_read_req {
+  /* out of prepare */
+  uint64_t total_len, total_head, total_tail;
+  /* out of complete */
+  uint64_t inline_off, inline_bytes, wr_bytes;
+  /* in */
+  uint32_t max_msg_sz;     /* port_.attr().max_msg_sz of the request's socket */
+  /* out of prepare */
+  int32_t status;
+  uint32_t failed_job;     /* index in d_jobs; HF3FS_SERVER_READ_NONE without a failure */
+  uint32_t n_small, n_big;
+  /* out of complete */
+  uint32_t n_ok, wr_first, wr_count, wr_fails;
+  /* in */
+  uint8_t checksum_type;   /* BatchReadReq::checksumType */
+  uint8_t xmit;            /* HF3FS_SERVER_READ_XMIT_* */
+  uint8_t read_uncommitted, recalculate;
+  uint8_t reserved[40];
+} hf3fs_crc_server_read_req;   /* 128 bytes */
+
+typedef struct hf3fs_crc_server_read_wr {
+  uint64_t remote_addr, local_addr;
+  uint32_t length, rkey, job, req;
+} hf3fs_crc_server_read_wr;    /* 32 bytes */
+
+enum {
+  HF3FS_SERVER_READ_XMIT_RDMA = 0,    /* neither flag: addBufferToBatch */
+  HF3FS_SERVER_READ_XMIT_INLINE = 1,  /* FeatureFlags::SEND_DATA_INLINE: copyToRespBuffer */
+  HF3FS_SERVER_READ_XMIT_NONE = 2     /* FeatureFlags::BYPASS_RDMAXMIT */
+};
+enum { HF3FS_SERVER_READ_BUF_NONE = 0, HF3FS_SERVER_READ_BUF_SMALL = 1, HF3FS_SERVER_READ_BUF_BIG = 2 };
+#define HF3FS_SERVER_READ_NONE 0xFFFFFFFFu
+enum {
+  /* hf3fs_crc_server_read_prepare */
+  HF3FS_SERVER_READ_INFO_REQS_OK = 0,
+  HF3FS_SERVER_READ_INFO_REQS_FAILED = 1,
+  HF3FS_SERVER_READ_INFO_JOBS_OK = 2,      /* jobs with status 0 */
+  HF3FS_SERVER_READ_INFO_JOBS_FAILED = 3,
+  HF3FS_SERVER_READ_INFO_SMALL = 4,        /* buffers over the passing requests */
+  HF3FS_SERVER_READ_INFO_BIG = 5,
+  /* hf3fs_crc_server_read_complete */
+  HF3FS_SERVER_READ_DONE_OK = 0,           /* jobs with result_status 0 */
+  HF3FS_SERVER_READ_DONE_FAILED = 1,
+  HF3FS_SERVER_READ_DONE_INLINE_LO = 2,    /* bytes the inline arena needs, 64 bits */
+  HF3FS_SERVER_READ_DONE_INLINE_HI = 3,
+  HF3FS_SERVER_READ_DONE_INLINE_OVERFLOW = 4, /* 1: they exceed inline_cap, no inline byte was stored */
+  HF3FS_SERVER_READ_DONE_WR = 5,           /* RDMA writes listed (the full count, beyond wr_cap too) */
+  HF3FS_SERVER_READ_DONE_WR_FAILS = 6,
+  HF3FS_SERVER_READ_DONE_HASHED = 7,       /* jobs whose bytes were hashed */
+  HF3FS_SERVER_READ_INFO_WORDS = 8         /* both calls; words without a name are written as 0 */
+};
+
+/* The server's half of batchRead around the AIO, as two stream-ordered calls (DESIGN.md 3.11,
+ * INTEGRATION.md 2.7).  Reference lines are of src/storage/.
+ *
+ * hf3fs_crc_server_read_prepare covers service/StorageOperator.cc:98-155, aio/BatchReadJob.cc:16-22,
+ * store/ChunkReplica.cc:38-76 and store/ChunkEngine.h:34-73, per request in job order:
+ *
+ * 1. Alignment (BatchReadJob.cc:20-21), in the reference's wrapping uint32_t arithmetic:
+ *    head_len = offset % 4096, tail_len = (4096 - (offset + length) % 4096) % 4096, read_len =
+ *    length + head_len + tail_len (always a multiple of 4096).
+ * 2. The first loop (StorageOperator.cc:101-130).  The first job that fails ends the request;
+ *    within a job: target_status != 0 gives that code (:107-111), !up_to_date 4032 (:113-117),
+ *    length > rdmabuf_size 3 (:122-128).  total_len / total_head / total_tail cover the jobs of a
+ *    request that passes this loop, and are 0 for one that does not.
+ * 3. The carve (StorageOperator.cc:141-154 over BufferPool::Buffer::tryAllocate / allocate,
+ *    service/BufferPool.cc:102-141), only after the first loop has passed every job: a next-fit
+ *    walk.  With no current buffer, or fewer than read_len bytes left in it, a new one is taken:
+ *    read_len > big_buf fails the request with 2019 (the reference answers kRDMANoBuf for every
+ *    allocation failure, :147-151), read_len > small_buf takes a big buffer, anything else a small
+ *    one.  The job takes read_len bytes from the current buffer, big or small; later jobs go on
+ *    taking from it.  buf_ordinal counts the request's buffers from 0 in the order taken, buf_kind
+ *    is the buffer's kind and buf_off the offset in it; n_small and n_big count the request's
+ *    buffers (0 for a failed request).  alignBuffer (:17-25) never moves: every read_len is a
+ *    multiple of 4096.
+ * 4. A failed request: status is the code, failed_job the failing job's index in d_jobs; every job
+ *    of it has that status, read_len 0 and no buffer.
+ * 5. Every job of a passing request, aioPrepareRead: meta_status != 0 is this job's status alone
+ *    (ChunkReplica.cc:46-50, ChunkEngine.h:48-54).  An engine job stores commit_ver := update_ver
+ *    in place (:61-62); its stored checksum reads as {CRC32C, ~chunk_checksum} (:65) in complete
+ *    and nothing is checked.  A replica job with commit_ver != update_ver and no read_uncommitted
+ *    gets 4004 (ChunkReplica.cc:61-66).  read_offset = inner_offset + (offset - head_len) (:72).
+ * Prepare loads and stores records only.  One lane walks one request: the walk is sequential by
+ * nature.  max_jobs_per_req (an upper bound of a request's jobs, 0 when unknown) has no effect at
+ * present: it is accepted so that a later schedule for long requests needs no new signature, and a
+ * request of many jobs is one lane's work.
+ *
+ * hf3fs_crc_server_read_complete covers aio/AioStatus.cc:27-55, aio/BatchReadJob.cc:24-113,
+ * store/ChunkReplica.cc:79-100, store/StorageTarget.cc:299-304 and common/net/ib/IBSocket.cc:258-275.
+ * A job whose prepare status is not 0 takes part in no rung: result_status is that status,
+ * result_len 0, the checksum {NONE, 0}.  A record this call cannot serve gets result_status 3 the
+ * same way: a request checksum_type or a stored checksum type that is neither NONE nor `type`, a
+ * clipped length above max_len, or a null localbuf under bytes that are hashed or packed.  The
+ * other jobs:
+ *
+ * 1. The length clip (AioStatus.cc:27-55): res < 0 gives 4010 with {NONE, 0}; otherwise L =
+ *    min(max(0, res - head_len), length, max(0, chunk_len - offset)) in signed 64 bits.
+ * 2. Rung 1 of setResult (BatchReadJob.cc:26-35) with the request's checksum_type T: NONE gives
+ *    {NONE, 0}; T equal to the stored type with offset == 0 and L == chunk_len gives the stored
+ *    checksum; anything else the raw CRC of [localbuf + head_len, +L), {T, ~0u} for L == 0 with
+ *    no byte read.
+ * 3. aioFinishRead (:38, StorageTarget.cc:299-304), replica jobs only: meta_status_now != 0 gives
+ *    that code, update_ver != update_ver_now 4004 (ChunkReplica.cc:85-98).
+ * 4. The recalculation (:43-54).  The reference dereferences lengthInfo here even when rung 3 has
+ *    just made it an error; this call skips the rung then.  With recalculate, offset == 0 and L ==
+ *    chunk_len the bytes are hashed with the stored type and a value other than the stored one
+ *    gives 4080; a NONE stored type mismatches exactly when its stored value is not 0.  The
+ *    same hashed range serves rungs 2 and 4.
+ *    On every error result_len is 0 and the checksum fields keep rung 2's value.
+ * 5. Inline (requests with xmit 1, BatchReadJob.cc:96-113): the L bytes of the jobs with
+ *    result_status 0 are concatenated in job order into d_inline, the requests back to back in
+ *    request order -- per request the layout StorageClientImpl.cc:1697-1717 consumes.  The job's
+ *    and the request's inline_off are set (a request's is where its first byte would go),
+ *    d_info holds the bytes needed.  When they exceed inline_cap no inline byte is stored at all
+ *    and HF3FS_SERVER_READ_DONE_INLINE_OVERFLOW is 1; every other output is set all the same.
+ * 6. The RDMA list (requests with xmit 0, BatchReadJob.cc:74-94): the jobs with result_status 0 in
+ *    job order; one with localbuf == 0, !has_rkey, L > rdmabuf_size or L > max_msg_sz
+ *    (IBSocket.cc:261-262) gets result_status 3 instead and counts in wr_fails.  A job of length
+ *    0 is listed: its buffer is valid.  d_wr receives the list up to wr_cap entries,
+ *    d_info[HF3FS_SERVER_READ_DONE_WR] its full length; a request's writes are wr_first,
+ *    wr_count of the full list.
+ * n_ok counts a request's jobs with result_status 0.
+ *
+ * Only the existing range kernels load bytes of [localbuf + head_len, +L) to hash, and only of
+ * the jobs that hash.  The inline pack is the library's one kernel that stores payload bytes to a
+ * caller buffer: a launch of its own behind the hash, the copy body of the update apply.
+ *
+ * The host keeps: BYPASS_DISKIO requests, the chunk lookup itself (it hands in meta_status and the
+ * metadata), the buffer semaphore and the turning of buf_ordinal into addresses, the AIO, the RDMA
+ * post and its failure fan-out (StorageOperator.cc:219-223), fault injection.
+ *
+ * Both calls: asynchronous on `stream`, nothing synchronised or read back; capturable, also as a
+ * process's first library calls, and a replayed graph works from what the records hold at replay
+ * time.  d_info (HF3FS_SERVER_READ_INFO_WORDS words) is set, not accumulated.
+ * HF3FS_CRC_INVALID_ARG before a device is touched: a type other than CRC32C / CRC32 (complete),
+ * null d_jobs with n > 0, null d_reqs or null d_req_off with n_reqs > 0, n > 0 with n_reqs == 0,
+ * null d_info, n or n_reqs above 2^30, inline_cap > 0 with null d_inline, wr_cap > 0 with null
+ * d_wr. */
+int hf3fs_crc_server_read_prepare(hf3fs_crc_server_read_job *d_jobs, uint64_t n,
+                                  hf3fs_crc_server_read_req *d_reqs, const uint64_t *d_req_off, uint64_t n_reqs,
+                                  uint64_t max_jobs_per_req, uint32_t small_buf, uint32_t big_buf,
+                                  uint32_t *d_info, void *stream);
+int hf3fs_crc_server_read_complete(uint8_t type, hf3fs_crc_server_read_job *d_jobs, uint64_t n,
+                                   hf3fs_crc_server_read_req *d_reqs, const uint64_t *d_req_off, uint64_t n_reqs,
+                                   uint32_t max_len, void *d_inline, uint64_t inline_cap,
+                                   hf3fs_crc_server_read_wr *d_wr, uint64_t wr_cap, uint32_t *d_info, void *stream);
+/* An upper bound of the library-owned scratch complete takes for n jobs of n_reqs requests on any
+ * device (prepare takes none).  Monotone in n, 0 for counts above 2^30. */
+size_t hf3fs_crc_server_read_scratch_bytes(uint64_t n, uint64_t n_reqs);
+
+/* ------------------------------------------------------------------------ */
 /* file MD5: admin `checksum --md5`                                           */
 /* ------------------------------------------------------------------------ */
 /* One run of bytes of a file, in file order. data == 0: `length` zero bytes (a hole). */
@@ -1463,5 +1661,34 @@ static_assert(offsetof(hf3fs_crc_forward_job, fwd_checksum_type) == 141 &&
                   offsetof(hf3fs_crc_forward_job, final_action) == 184 &&
                   offsetof(hf3fs_crc_forward_job, buffer_corrupted) == 185,
               "forward job response and complete outputs");
+/* The server read records' layouts are part of the ABI (3fs_amd/_lib.py mirrors them). */
+static_assert(sizeof(hf3fs_crc_server_read_job) == 192 && sizeof(hf3fs_crc_server_read_job) % 64 == 0,
+              "server read job size");
+static_assert(offsetof(hf3fs_crc_server_read_job, localbuf) == 16 && offsetof(hf3fs_crc_server_read_job, res) == 24 &&
+                  offsetof(hf3fs_crc_server_read_job, read_offset) == 32 &&
+                  offsetof(hf3fs_crc_server_read_job, inline_off) == 40 &&
+                  offsetof(hf3fs_crc_server_read_job, offset) == 48 &&
+                  offsetof(hf3fs_crc_server_read_job, target_status) == 64 &&
+                  offsetof(hf3fs_crc_server_read_job, meta_status_now) == 92 &&
+                  offsetof(hf3fs_crc_server_read_job, head_len) == 100 &&
+                  offsetof(hf3fs_crc_server_read_job, status) == 120 &&
+                  offsetof(hf3fs_crc_server_read_job, result_len) == 124 &&
+                  offsetof(hf3fs_crc_server_read_job, has_rkey) == 136 &&
+                  offsetof(hf3fs_crc_server_read_job, buf_kind) == 140 &&
+                  offsetof(hf3fs_crc_server_read_job, checksum_type) == 141,
+              "server read job layout");
+static_assert(sizeof(hf3fs_crc_server_read_req) == 128 && sizeof(hf3fs_crc_server_read_req) % 64 == 0,
+              "server read request size");
+static_assert(offsetof(hf3fs_crc_server_read_req, inline_off) == 24 && offsetof(hf3fs_crc_server_read_req, wr_bytes) == 40 &&
+                  offsetof(hf3fs_crc_server_read_req, max_msg_sz) == 48 &&
+                  offsetof(hf3fs_crc_server_read_req, status) == 52 &&
+                  offsetof(hf3fs_crc_server_read_req, n_ok) == 68 &&
+                  offsetof(hf3fs_crc_server_read_req, wr_fails) == 80 &&
+                  offsetof(hf3fs_crc_server_read_req, checksum_type) == 84 &&
+                  offsetof(hf3fs_crc_server_read_req, recalculate) == 87,
+              "server read request layout");
+static_assert(sizeof(hf3fs_crc_server_read_wr) == 32 && offsetof(hf3fs_crc_server_read_wr, length) == 16 &&
+                  offsetof(hf3fs_crc_server_read_wr, req) == 28,
+              "server read write-list entry layout");
 #endif
 #endif /* HF3FS_CRC_H */
