@@ -47,4 +47,8 @@ from ._lib import (CHUNK_METADATA_GET_ERROR, CHUNK_METADATA_NOT_FOUND, CHUNK_NOT
                    SERVER_READ_XMIT_INLINE, SERVER_READ_XMIT_NONE, SERVER_READ_XMIT_RDMA, TARGET_STATE_INVALID,
                    ServerReadJob, ServerReadReq, ServerReadWr, server_read_complete, server_read_job_dtype,
                    server_read_prepare, server_read_req_dtype, server_read_scratch_bytes, server_read_wr_dtype)
+from ._lib import (DATA_CORRUPTION, FILE_LEN_DYN, FILE_LEN_INFO_NAMES, FILE_LEN_INFO_WORDS,  # noqa: F401
+                   FILE_LEN_MAX_OPS, META_BUSY, RANGE_INFO_NAMES, RANGE_INFO_WORDS, RANGE_MAX_COUNT, RANGE_NONE,
+                   RANGE_QUERY, RANGE_REMOVE, FileLen, RangeOp, file_len_dtype, file_length, range_op_dtype,
+                   range_query, range_query_scratch_bytes, sync_meta_dtype)
 from .checksum import ChecksumInfo, ChecksumType  # noqa: F401

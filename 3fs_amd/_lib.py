@@ -375,6 +375,44 @@ SYNC_INFO_NAMES = ("fatal", "first_fatal", "n_write", "n_remove", "recycle", "ch
                    "full_sync_light", "skip", "remote_miss", "duplicates")
 
 
+class RangeOp(ctypes.Structure):
+    """hf3fs_crc_range_op: one QueryLastChunkOp or RemoveChunksOp payload, a walk over one target's
+    chunk metadata by chunk-id range (StorageOperator.cc:653-751,858-1000)."""
+    _fields_ = [
+        ("begin_hi", _u64c), ("begin_lo", _u64c), ("end_hi", _u64c), ("end_lo", _u64c),
+        ("max_chunks", _u32c), ("status_in", _i32c), ("kind", _u8c), ("reserved0", _u8c * 3), ("chain_id", _u32c),
+        # out
+        ("last_hi", _u64c), ("last_lo", _u64c), ("total_len", _u64c),
+        ("total_chunks", _u32c), ("last_len", _u32c), ("last_index", _u32c), ("list_first", _u32c),
+        ("status", _i32c), ("more", _u8c), ("reserved1", _u8c * 3),
+    ]
+
+
+class FileLen(ctypes.Structure):
+    """hf3fs_crc_file_len: one file of the meta service's length fold (FileOperation.cc:45-179)."""
+    _fields_ = [
+        ("inode", _u64c), ("first_op", _u32c), ("n_file_ops", _u32c), ("chunk_size", _u32c), ("stripe_size", _u32c),
+        ("flags", _u8c), ("reserved", _u8c * 3),
+        # out
+        ("status", _i32c), ("length", _u64c), ("total_len", _u64c), ("total_chunks", _u64c),
+        ("last_chunk", _u32c), ("last_chunk_len", _u32c),
+    ]
+
+
+assert ctypes.sizeof(RangeOp) == 96 and ctypes.sizeof(FileLen) == 64
+RANGE_QUERY, RANGE_REMOVE = 1, 2  # RangeOp.kind
+RANGE_NONE = 0xFFFFFFFF  # RangeOp.last_index: no chunk; a saturated list_first
+RANGE_INFO_WORDS = 8
+RANGE_INFO_NAMES = ("ops_ok", "ops_failed", "chunks_lo", "chunks_hi", "list_lo", "list_hi", "list_overflow",
+                    "unsorted")
+RANGE_MAX_COUNT = 1 << 30
+FILE_LEN_DYN = 1  # FileLen.flags
+FILE_LEN_MAX_OPS = 1024
+FILE_LEN_INFO_WORDS = 8
+FILE_LEN_INFO_NAMES = ("ok", "failed", "empty", "not_found", "busy", "corrupt", "reserved6", "reserved7")
+DATA_CORRUPTION, META_BUSY = 2, 3019  # StatusCode::kDataCorruption, MetaCode::kBusy
+
+
 class Frame(ctypes.Structure):
     """hf3fs_crc_frame: one serde message of a receive buffer."""
     _fields_ = [
@@ -492,6 +530,9 @@ SIGNATURES = {
     "hf3fs_crc_server_read_prepare": (_int, [_vp, _u64, _vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp]),
     "hf3fs_crc_server_read_complete": (_int, [_u8, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
     "hf3fs_crc_server_read_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
+    "hf3fs_crc_range_query": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "hf3fs_crc_range_query_scratch_bytes": (ctypes.c_size_t, [_u64, _u64]),
+    "hf3fs_crc_file_length": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
     "hf3fs_crc_file_digest_batch": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "hf3fs_crc_file_digest_batch_ex": (_int, [_vp, _vp, _vp, _u64, _u64, _u32, _vp]),
     "hf3fs_crc_md5_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp]),
@@ -902,6 +943,42 @@ def server_read_complete(ctype, jobs, n, reqs, req_off, n_reqs, info, max_len, i
 def server_read_scratch_bytes(n, n_reqs=0):
     """Bytes of library-owned scratch complete takes for n jobs of n_reqs requests (0: rejected counts)."""
     return int(load().hf3fs_crc_server_read_scratch_bytes(n, n_reqs))
+
+
+def range_op_dtype():
+    """numpy dtype of hf3fs_crc_range_op: one 96-byte record per range walk."""
+    return _record_dtype(RangeOp)
+
+
+def file_len_dtype():
+    """numpy dtype of hf3fs_crc_file_len: one 64-byte record per file."""
+    return _record_dtype(FileLen)
+
+
+def sync_meta_dtype():
+    """numpy dtype of hf3fs_crc_sync_meta: the table record of sync_plan and range_query."""
+    import numpy as np
+    kinds = {ctypes.c_uint8: "u1", ctypes.c_uint32: "<u4", ctypes.c_uint64: "<u8"}
+    return np.dtype([(name, kinds[t]) for name, t in SyncMeta._fields_])
+
+
+def range_query(meta, n_meta, ops, n_ops, info, list_out=None, list_cap=0, stream=None):
+    """hf3fs_crc_range_query: meta a device array of hf3fs_crc_sync_meta, strictly ascending by id
+    (read only), ops a device array of hf3fs_crc_range_op (outputs written in place), list_out
+    list_cap device u32 or None, info RANGE_INFO_WORDS device u32."""
+    return check(load().hf3fs_crc_range_query(_p(meta), n_meta, _p(ops), n_ops, _p(list_out), list_cap, _p(info),
+                                              _s(stream)))
+
+
+def range_query_scratch_bytes(n_meta, n_ops):
+    """Bytes of library-owned scratch one range_query of this shape takes (0: rejected counts)."""
+    return int(load().hf3fs_crc_range_query_scratch_bytes(n_meta, n_ops))
+
+
+def file_length(ops, n_ops, files, n_files, info, stream=None):
+    """hf3fs_crc_file_length: ops finished range ops (read only), files a device array of
+    hf3fs_crc_file_len (outputs written in place), info FILE_LEN_INFO_WORDS device u32."""
+    return check(load().hf3fs_crc_file_length(_p(ops), n_ops, _p(files), n_files, _p(info), _s(stream)))
 
 
 MD5_INIT, MD5_FINAL = 1, 2  # hf3fs_crc_md5_batch flags

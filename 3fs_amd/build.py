@@ -13,15 +13,15 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libhf3fs_crc.so")
-SOURCES = ["crc_kernels.hip", "update_kernels.hip", "order_kernels.hip", "version_kernels.hip", "engine_kernels.hip", "sync_kernels.hip", "client_read_kernels.hip", "client_write_kernels.hip", "forward_kernels.hip", "server_read_kernels.hip", "digest_kernels.hip", "md5_kernels.hip", "hf3fs_crc_api.hip",
+SOURCES = ["crc_kernels.hip", "update_kernels.hip", "order_kernels.hip", "version_kernels.hip", "engine_kernels.hip", "sync_kernels.hip", "client_read_kernels.hip", "client_write_kernels.hip", "forward_kernels.hip", "server_read_kernels.hip", "range_kernels.hip", "digest_kernels.hip", "md5_kernels.hip", "hf3fs_crc_api.hip",
            "capture_scratch.hip", "device_tables.cc", "coalescer.hip", "aux_kernels.hip", "frame_kernels.hip", "host_codec.cc", "options.cc"]
-HEADERS = ["loadcheck.h", "crc_kernels.h", "crc_device.h", "update_kernels.h", "update_plan.h", "order_kernels.h", "version_kernels.h", "version_plan.h", "engine_kernels.h", "engine_plan.h", "sync_kernels.h", "sync_plan.h", "client_read_kernels.h", "client_read_plan.h", "client_write_kernels.h", "client_write_plan.h", "forward_kernels.h", "forward_plan.h", "server_read_kernels.h", "server_read_plan.h", "copy_range.h", "compact.h", "digest_kernels.h", "md5_kernels.h", "md5_core.h", "gf2.h", "internal.h", "capture_scratch.h", "aux_kernels.h", "frame_kernels.h", "options.h"]
+HEADERS = ["loadcheck.h", "crc_kernels.h", "crc_device.h", "update_kernels.h", "update_plan.h", "order_kernels.h", "version_kernels.h", "version_plan.h", "engine_kernels.h", "engine_plan.h", "sync_kernels.h", "sync_plan.h", "client_read_kernels.h", "client_read_plan.h", "client_write_kernels.h", "client_write_plan.h", "forward_kernels.h", "forward_plan.h", "server_read_kernels.h", "server_read_plan.h", "range_kernels.h", "range_plan.h", "copy_range.h", "compact.h", "digest_kernels.h", "md5_kernels.h", "md5_core.h", "gf2.h", "internal.h", "capture_scratch.h", "aux_kernels.h", "frame_kernels.h", "options.h"]
 ARCH = os.environ.get("HF3FS_CRC_ARCH", "gfx950")
 # The load-checked library (csrc/loadcheck.h, tests/test_gpu_load_footprint.py): the units whose
 # kernels load caller bytes are compiled again with the switch, the others' objects are shared.
 CHECK_LIB = os.path.join(LIBDIR, "libhf3fs_crc_loadcheck.so")
 CHECK_SOURCES = ["crc_kernels.hip", "update_kernels.hip", "frame_kernels.hip", "md5_kernels.hip", "aux_kernels.hip",
-                 "order_kernels.hip", "version_kernels.hip", "engine_kernels.hip", "client_read_kernels.hip", "client_write_kernels.hip", "forward_kernels.hip", "server_read_kernels.hip"]
+                 "order_kernels.hip", "version_kernels.hip", "engine_kernels.hip", "client_read_kernels.hip", "client_write_kernels.hip", "forward_kernels.hip", "server_read_kernels.hip", "range_kernels.hip"]
 CHECK_ONLY = ["loadcheck.hip"]
 
 

@@ -36,6 +36,8 @@
 #include "md5_kernels.h"
 #include "options.h"
 #include "order_kernels.h"
+#include "range_kernels.h"
+#include "range_plan.h"  // kRangeMaxCount
 #include "server_read_kernels.h"
 #include "server_read_plan.h"  // kServerReadMaxCount
 #include "sync_kernels.h"
@@ -1630,6 +1632,47 @@ int hf3fs_crc_sync_plan(hf3fs_crc_sync_meta* d_local, uint64_t n_local, hf3fs_cr
   SyncScratch ss;
   sync_scratch_carve(base, n_local, n_remote, &ss);
   HIP_OR_FAIL(launch_sync_plan(d_local, n_local, d_remote, n_remote, chain_ver, flags, d_write, d_remove, d_info, ss, s));
+  return HF3FS_CRC_OK;
+}
+
+size_t hf3fs_crc_range_query_scratch_bytes(uint64_t n_meta, uint64_t n_ops) {
+  if (n_meta > kRangeMaxCount || n_ops > kRangeMaxCount) return 0;
+  return range_scratch_bytes(n_meta, n_ops);
+}
+
+int hf3fs_crc_range_query(const hf3fs_crc_sync_meta* d_meta, uint64_t n_meta, hf3fs_crc_range_op* d_ops, uint64_t n_ops,
+                          uint32_t* d_list, uint64_t list_cap, uint32_t* d_info, void* stream) {
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if ((!d_meta && n_meta) || (!d_ops && n_ops)) return fail(HF3FS_CRC_INVALID_ARG, "null table or ops");
+  if (n_meta > kRangeMaxCount || n_ops > kRangeMaxCount)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many records or ops (%llu, %llu)", (unsigned long long)n_meta,
+                (unsigned long long)n_ops);
+  if (!d_list && list_cap) return fail(HF3FS_CRC_INVALID_ARG, "null list");
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // Empty arrays take the same launches (every loop is empty): d_info becomes the empty result.
+  void* base = nullptr;
+  if (int rc = call_scratch(c, s, range_scratch_bytes(n_meta, n_ops), &base)) return rc;
+  RangeScratch rs;
+  range_scratch_carve(base, n_meta, n_ops, &rs);
+  HIP_OR_FAIL(launch_range_query(d_meta, n_meta, d_ops, n_ops, d_list, list_cap, d_info, rs, s));
+  return HF3FS_CRC_OK;
+}
+
+int hf3fs_crc_file_length(const hf3fs_crc_range_op* d_ops, uint64_t n_ops, hf3fs_crc_file_len* d_files,
+                          uint64_t n_files, uint32_t* d_info, void* stream) {
+  if (!d_info) return fail(HF3FS_CRC_INVALID_ARG, "null info");
+  if ((!d_ops && n_ops) || (!d_files && n_files)) return fail(HF3FS_CRC_INVALID_ARG, "null ops or files");
+  if (n_ops > kRangeMaxCount || n_files > kRangeMaxCount)
+    return fail(HF3FS_CRC_INVALID_ARG, "too many ops or files (%llu, %llu)", (unsigned long long)n_ops,
+                (unsigned long long)n_files);
+  Context* c = nullptr;
+  if (int rc = get_context(&c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OR_FAIL(launch_zero_words(d_info, HF3FS_FILE_LEN_INFO_WORDS, s));  // the kernel adds into it
+  if (n_files == 0) return HF3FS_CRC_OK;
+  HIP_OR_FAIL(launch_file_length(d_ops, n_ops, d_files, n_files, d_info, s));
   return HF3FS_CRC_OK;
 }
 

@@ -1492,6 +1492,129 @@ size_t hf3fs_crc_sync_plan_scratch_bytes(uint64_t n_local, uint64_t n_remote);
 int hf3fs_crc_sync_scrub_fill(const hf3fs_crc_sync_meta *d_local, const uint64_t *d_addrs, const uint32_t *d_write,
                               const uint32_t *d_info, uint64_t n_local, hf3fs_crc_scrub_io *d_scrub, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* chunk range walks: queryLastChunk, removeChunks and the file-length fold  */
+/* ------------------------------------------------------------------------ */
+/* One QueryLastChunkOp or RemoveChunksOp payload: a walk over one target's chunk metadata by
+ * chunk-id range (StorageOperator::queryLastChunk, src/storage/service/StorageOperator.cc:858-916,
+ * and ::removeChunks, :936-1000, both through processQueryResults, :653-751, over
+ * ChunkStore::queryChunks, src/storage/store/ChunkStore.cc:120-147).  Ids compare as the unsigned
+ * pair (hi, lo): the byte order of ChunkId(high, low) (Common.cc:10-18). */
+typedef struct hf3fs_crc_range_op {
+  uint64_t begin_hi, begin_lo; /* ChunkIdRange [begin, end) */
+  uint64_t end_hi, end_lo;
+  uint32_t max_chunks;         /* maxNumChunkIdsToProcess; 0 = unlimited */
+  int32_t status_in;           /* a failure the host found before the walk (getByChainId, :638); non-zero:
+                                  status = status_in and nothing is walked */
+  uint8_t kind;                /* HF3FS_RANGE_QUERY or HF3FS_RANGE_REMOVE; anything else: status 3 */
+  uint8_t reserved0[3];
+  uint32_t chain_id;           /* carried; hf3fs_crc_file_length reads it */
+  uint64_t last_hi, last_lo;   /* out: lastChunkId, the highest processed id; 0, 0 when none */
+  uint64_t total_len;          /* out: totalChunkLen, the sum of the processed records' length */
+  uint32_t total_chunks;       /* out: totalNumChunks / the upper bound of numChunksRemoved */
+  uint32_t last_len;           /* out: lastChunkLen */
+  uint32_t last_index;         /* out: table index of the last chunk, 0xFFFFFFFF when none */
+  uint32_t list_first;         /* out: where the op's segment of d_list begins (0xFFFFFFFF: past 32 bits) */
+  int32_t status;              /* out: 0, status_in, or 3 (bad kind, unsorted table) */
+  uint8_t more;                /* out: moreChunksInRange */
+  uint8_t reserved1[3];
+} hf3fs_crc_range_op;
+
+enum { HF3FS_RANGE_QUERY = 1, HF3FS_RANGE_REMOVE = 2 };
+
+/* Words of hf3fs_crc_range_query's d_info. */
+enum {
+  HF3FS_RANGE_INFO_OPS_OK = 0,     /* ops with status 0 */
+  HF3FS_RANGE_INFO_OPS_FAILED = 1, /* ops with status != 0 */
+  HF3FS_RANGE_INFO_CHUNKS_LO = 2,  /* the sum of total_chunks, 64 bits */
+  HF3FS_RANGE_INFO_CHUNKS_HI = 3,
+  HF3FS_RANGE_INFO_LIST_LO = 4,    /* list entries of all REMOVE ops, 64 bits (also past list_cap) */
+  HF3FS_RANGE_INFO_LIST_HI = 5,
+  HF3FS_RANGE_INFO_OVERFLOW = 6,   /* 1 when the list entries exceed list_cap */
+  HF3FS_RANGE_INFO_UNSORTED = 7,   /* indices i >= 1 with id[i-1] >= id[i] */
+  HF3FS_RANGE_INFO_WORDS = 8
+};
+
+/* n_ops range walks over one target's table d_meta[0, n_meta) (the layout hf3fs_crc_sync_plan takes,
+ * read only here), as one stream-ordered call.  The table must be strictly ascending by (id_hi,
+ * id_lo); the call counts the indices that break the order in d_info[UNSORTED], and when there is
+ * one every op gets status 3, no outputs and an empty list segment.
+ * Per op, the closed form of the paged loop (:653-751):
+ *   span          the records with begin <= id < end (none when begin >= end)
+ *   normals       the span's records with recycle_state == 0 (:677-696 skips the others)
+ *   limit         max_chunks ? min(max_chunks, 2^32 - 2) : 2^32 - 2 (:658-660)
+ *   total_chunks  min(normals, limit);  more = normals > limit
+ *   processed     the total_chunks normal records of the span with the highest ids (the walk
+ *                 descends from `end`); last_* describe the highest, total_len sums their length
+ * The page size max_num_results_per_query changes no output.  An op that is not walked (status !=
+ * 0) has last_index 0xFFFFFFFF and every other output 0 but list_first and status.
+ * The list: a REMOVE op's processed records' table indices go to d_list[list_first, list_first +
+ * total_chunks), highest id first: the order in which removeChunks issues doRemove (:949-971).
+ * Segments lie in op order, list_first is the sum of the earlier ops' list counts (a QUERY op lists
+ * nothing and carries the running offset), entries at positions >= list_cap are not written (d_info
+ * has the full count and the overflow flag).  Ranges of different ops may overlap.
+ * Errors, all checked before any device is touched: null d_info, a null array with a non-zero
+ * count, n_meta or n_ops above 2^30, null d_list with list_cap > 0 -> kInvalidArg.  Both counts 0 is
+ * OK: d_info is the empty result.
+ * Stream behaviour follows hf3fs_crc_sync_plan: asynchronous on `stream`, no host synchronisation,
+ * nothing read back; capturable, also as the process's first library call; a replayed graph
+ * re-plans from what table and ops hold at replay time.  Scratch per (stream, thread) pair outside
+ * a capture and graph-owned inside one; every scratch word read is written by the call first. */
+int hf3fs_crc_range_query(const hf3fs_crc_sync_meta *d_meta, uint64_t n_meta, hf3fs_crc_range_op *d_ops,
+                          uint64_t n_ops, uint32_t *d_list, uint64_t list_cap, uint32_t *d_info, void *stream);
+/* Bytes of scratch one such call takes; 0 for counts the call rejects. */
+size_t hf3fs_crc_range_query_scratch_bytes(uint64_t n_meta, uint64_t n_ops);
+
+/* One file of the meta service's length query (FileOperation::queryChunksByChain / queryChunks,
+ * src/fbs/meta/FileOperation.cc:45-179): its ops are d_ops[first_op, first_op + n_file_ops), the
+ * file's stripes in order; n_file_ops is the reference's maxStripe. */
+typedef struct hf3fs_crc_file_len {
+  uint64_t inode;
+  uint32_t first_op, n_file_ops;
+  uint32_t chunk_size, stripe_size; /* layout.chunkSize, layout.stripeSize */
+  uint8_t flags;                    /* HF3FS_FILE_LEN_DYN: dynStripe && inode.dynStripe */
+  uint8_t reserved[3];
+  int32_t status;                   /* out: 0, an op's status, 2, 3019, or 3 (a bad record) */
+  uint64_t length;                  /* out: the greatest chunk * chunk_size + last_len over the chains */
+  uint64_t total_len;               /* out: totalChunkLen, summed over the chains */
+  uint64_t total_chunks;            /* out: totalNumChunks, summed over the chains */
+  uint32_t last_chunk;              /* out: the winning chain's lastChunk */
+  uint32_t last_chunk_len;          /* out: its lastChunkLen */
+} hf3fs_crc_file_len;
+
+enum { HF3FS_FILE_LEN_DYN = 1 };
+enum { HF3FS_FILE_LEN_MAX_OPS = 1024 };
+
+/* Words of hf3fs_crc_file_length's d_info. */
+enum {
+  HF3FS_FILE_LEN_INFO_OK = 0,        /* files with status 0 */
+  HF3FS_FILE_LEN_INFO_FAILED = 1,    /* files with status != 0 */
+  HF3FS_FILE_LEN_INFO_EMPTY = 2,     /* files with status 0 and no surviving op */
+  HF3FS_FILE_LEN_INFO_NOT_FOUND = 3, /* ops skipped for status 7007 (those before a file's first failing op) */
+  HF3FS_FILE_LEN_INFO_BUSY = 4,      /* files with status 3019 */
+  HF3FS_FILE_LEN_INFO_CORRUPT = 5,   /* files with status 2 */
+  HF3FS_FILE_LEN_INFO_WORDS = 8      /* words 6 and 7 are 0 */
+};
+
+/* The fold of n_files files over finished range ops (d_ops is read only).  Per file, over its ops in
+ * order (:127-176): status 7007 (kChunkNotFound) skips the op; any other non-zero status ends the
+ * file with that code; total_chunks == 0 skips the op; last id == meta::ChunkId(InodeId(-1), 0, 0)
+ * or inode(id) != inode ends the file with 2 (kDataCorruption), where inode(id) = ((last_hi &
+ * 0xFFFFFFFFFFFF) << 16) | (last_lo >> 48) and chunk(id) = last_lo & 0xFFFFFFFF (the big-endian
+ * layout of src/fbs/meta/Schema.h:177-226); with DYN set, n_file_ops < stripe_size and chunk(id) >=
+ * n_file_ops the file ends with 3019 (MetaCode::kBusy).  Otherwise the op enters the map under its
+ * chain_id with length = chunk(id) * chunk_size + last_len (64 bits), replacing an earlier op of
+ * the file with that chain_id.  The fold (:45-76), in ascending chain_id: the greatest length wins,
+ * on equal lengths the lowest chain_id; total_len and total_chunks sum the map's entries.  A file
+ * with no entry is all zeros with status 0; a file that ends with a code has that status and zero
+ * outputs.  The kFoundBug check (:70) cannot fire with this arithmetic.
+ * Bad records get status 3 and read no op: first_op + n_file_ops > n_ops, n_file_ops > 1024.
+ * Segments of different files may overlap.
+ * Errors before any device is touched: null d_info, a null array with a non-zero count, n_ops or
+ * n_files above 2^30 -> kInvalidArg.  Stream, capture and poison contract as above; no scratch. */
+int hf3fs_crc_file_length(const hf3fs_crc_range_op *d_ops, uint64_t n_ops, hf3fs_crc_file_len *d_files,
+                          uint64_t n_files, uint32_t *d_info, void *stream);
+
 /* The chunk engine's persisted ChunkMeta (chunk_meta.rs:7-20) in its derse
  * wire form: a one-byte body length, then pos u64, chain_ver, chunk_ver, len,
  * checksum (u32 each), timestamp, last_request_id, last_client_low/high (u64
@@ -1690,5 +1813,20 @@ static_assert(offsetof(hf3fs_crc_server_read_req, inline_off) == 24 && offsetof(
 static_assert(sizeof(hf3fs_crc_server_read_wr) == 32 && offsetof(hf3fs_crc_server_read_wr, length) == 16 &&
                   offsetof(hf3fs_crc_server_read_wr, req) == 28,
               "server read write-list entry layout");
+/* The range records' layouts are part of the ABI (3fs_amd/_lib.py mirrors them). */
+static_assert(sizeof(hf3fs_crc_range_op) == 96 && offsetof(hf3fs_crc_range_op, max_chunks) == 32 &&
+                  offsetof(hf3fs_crc_range_op, status_in) == 36 && offsetof(hf3fs_crc_range_op, kind) == 40 &&
+                  offsetof(hf3fs_crc_range_op, chain_id) == 44 && offsetof(hf3fs_crc_range_op, last_hi) == 48 &&
+                  offsetof(hf3fs_crc_range_op, total_len) == 64 && offsetof(hf3fs_crc_range_op, total_chunks) == 72 &&
+                  offsetof(hf3fs_crc_range_op, last_len) == 76 && offsetof(hf3fs_crc_range_op, last_index) == 80 &&
+                  offsetof(hf3fs_crc_range_op, list_first) == 84 && offsetof(hf3fs_crc_range_op, status) == 88 &&
+                  offsetof(hf3fs_crc_range_op, more) == 92,
+              "range op layout");
+static_assert(sizeof(hf3fs_crc_file_len) == 64 && offsetof(hf3fs_crc_file_len, first_op) == 8 &&
+                  offsetof(hf3fs_crc_file_len, chunk_size) == 16 && offsetof(hf3fs_crc_file_len, flags) == 24 &&
+                  offsetof(hf3fs_crc_file_len, status) == 28 && offsetof(hf3fs_crc_file_len, length) == 32 &&
+                  offsetof(hf3fs_crc_file_len, total_chunks) == 48 && offsetof(hf3fs_crc_file_len, last_chunk) == 56 &&
+                  offsetof(hf3fs_crc_file_len, last_chunk_len) == 60,
+              "file length record layout");
 #endif
 #endif /* HF3FS_CRC_H */
